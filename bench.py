@@ -1,6 +1,6 @@
 """bench.py — images/sec of one full YOLOv5-s train step (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either torch.distributed.run starts the N ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment: the driver's
 form, reference README.md:127 `python -m torch.distributed.launch --nproc_per_node=N trainer.py`), or — when WORLD_SIZE is not
@@ -68,7 +68,14 @@ def parse():
     ap.add_argument("--no-exchange-ab", action="store_true", help="N > 1: skip the gradient-exchange legs (all-reduce vs reduce-scatter + all-gather, 8 vs 25 MiB buckets)")
     ap.add_argument("--allow-torch-dist", action="store_true", help="N > 1: if the native RCCL communicator cannot start, run over torch.distributed "
                     "(hipified ProcessGroupNCCL) and SAY SO in config.transport instead of failing")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (its loss terms, the "
+                    "updated parameters and BatchNorm statistics; not the EMA weights) as DIR/<name>.npy, float32 (rank 0). The whole run then "
+                    "uses the engine's deterministic reductions (ops.set_deterministic), so that the same arguments give the same outputs "
+                    "every run")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _free_port():
@@ -257,6 +264,26 @@ def timed_steps(step, imgs, gts, steps, barrier=None):
     el = time.perf_counter() - t0
     per = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
     return el, losses, _median(per), per
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, losses):
+    """--dump-outputs: what the last timed step hands its caller — the loss terms it returns and the model it updated (every parameter,
+    then every floating-point buffer, each set flattened in module order) — as float32 <path>/<name>.npy. The EMA copy of the weights,
+    which the fused step also updates, is left out (it would double the 28 MB of YOLOv5-s). The weights and the batch are seeded, so two
+    builds run with the same arguments can be compared array by array."""
+    import numpy as np
+    arrays = {k: v.detach().float().reshape(-1) for k, v in losses.items()}
+    arrays["parameters"] = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+    arrays["buffers"] = torch.cat([b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()])
+    total = sum(4 * v.numel() for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("[bench] --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.cpu().numpy())
 
 
 def _graph_step(step, imgs, gts, warmup, graph=True):
@@ -661,6 +688,15 @@ def main():
     from cvpytorch_amd.arena import FlatTrainState, FlatTrainStep
     from cvpytorch_amd.train import GradBucketer, ModelEMA, TrainStep, build_optimizer
 
+    if a.dump_outputs:
+        # Outputs meant for comparison must be the same every run. The default step is not: its weight-gradient flushes (split-K
+        # wgrad, fused 1x1 backward, stem patch-wgrad) accumulate with fp32 atomics, so two runs differ in the last bit after one
+        # step, and training amplifies that within a few steps (BatchNorm-bias gradients are near-cancelling sums at
+        # initialisation: up to 25 % apart after two steps). The dumping run therefore times and dumps the engine's fixed-order
+        # program (ops.set_deterministic: ordered wgrad folds, partial-row BatchNorm sums, no fused 1x1 backward, no lazy
+        # activations); config.deterministic says so, and the atomic kernels keep their own parity tests.
+        ops.set_deterministic(True)
+
     max_boxes = 20
 
     def build_step(sync_bn, grad_exchange="allreduce", bucket_mib=8):
@@ -735,7 +771,7 @@ def main():
                        "global_batch": gb, "parallelism": "dp%d" % world, "final_loss": round(loss_val, 4), "launch": launch,
                        "world": comm.world if comm is not None else 1, "transport": transport,
                        "grad_buckets": (len(state.buckets) if (state is not None and world > 1) else 0),
-                       "sync_bn": bool(a.sync_bn and world > 1),
+                       "sync_bn": bool(a.sync_bn and world > 1), "deterministic": ops.is_deterministic(),
                        "statistic": "value = global_batch * K / wall time of the K timed steps (max over ranks); *_median from per-step HIP events"},
         }
 
@@ -775,6 +811,8 @@ def main():
     ops.TIMER.reset()
     el, losses, med, per = timed_steps(step, imgs, gts, a.steps, barrier)
     ops.TIMER.enabled = False
+    if a.dump_outputs and rank == 0:   # before the eager re-run below, which trains the same model further
+        dump_outputs(a.dump_outputs, model, losses)
     timing_source = "HIP events around every conv launch inside the timed region (eager)"
     if use_graph and not a.no_kernel_timing:  # every rank takes part (the steps contain collectives); only rank 0 records events
         # per-kernel events cannot ride inside a graph replay: time the same K steps once more, eagerly, right after

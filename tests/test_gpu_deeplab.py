@@ -208,9 +208,16 @@ def test_deeplab_end_to_end_vs_oracle(output_stride):
     with torch.autocast("cpu", dtype=torch.bfloat16):
         l2 = ref2(imgs, tgt, "train")["loss"]
     l2.backward()
-    floor = np.median([cosine(p.grad.float(), rp[n].grad) for n, p in ref2.named_parameters()])
-    got = np.median([cosine(p.grad.float(), rp[n].grad) for n, p in hip.named_parameters()])
-    assert got > floor - 0.05, (got, floor)
+    # At this size the fp32 gradient below the head is chaotic: the oracle's own bf16 run keeps cosine ~0 with it there, and that
+    # median (~0.00 to ~0.08) depends on the host CPU's bf16 kernels. The gradients that survive bf16 storage in the oracle
+    # (cosine > 0.9: the classifier, the last fused BatchNorm) must survive it in the engine as well, each one. The backbone's
+    # gradients are pinned block by block, teacher-forced, in test_gpu_full_size.py::test_deeplabv3plus_512x1024_bottlenecks_teacher_forced_vs_oracle.
+    hp = dict(hip.named_parameters())
+    floor = {n: cosine(p.grad.float(), rp[n].grad) for n, p in ref2.named_parameters()}
+    kept = {n: (f, cosine(hp[n].grad.float(), rp[n].grad)) for n, f in floor.items() if f > 0.9}
+    assert len(kept) >= 2 and "head.cls_seg.weight" in kept, sorted(kept)
+    for n, (f, got) in kept.items():
+        assert got > f - 0.05, (n, got, f)
     rb = dict(ref.named_buffers())
     for n, b in hip.named_buffers():
         if "running_mean" in n and "layer1.0" in n:

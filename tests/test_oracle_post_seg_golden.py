@@ -80,7 +80,12 @@ def test_yolox_post_process_equals_reference(name):
         if r is None:
             assert a is None
         else:
-            assert torch.equal(a, r)
+            # kept rows, their order and classes: bit-exact. Boxes (exp) and scores (sigmoid) are rounded by torch's CPU vector-math
+            # path, which differs between hosts: within 1e-6 of the largest value of each group (~8 float32 ulps of it; observed
+            # differences stay below 0.4 ulp of the largest box coordinate and 1 ulp of the scores)
+            assert a.shape == r.shape and torch.equal(a[:, 6], r[:, 6])
+            close(a[:, :4], r[:, :4], rtol=1e-6, atol=0.0)
+            close(a[:, 4:6], r[:, 4:6], rtol=1e-6, atol=0.0)
 
 
 @pytest.mark.parametrize("name", ["plain", "split", "agnostic"])
