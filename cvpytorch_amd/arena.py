@@ -204,10 +204,6 @@ class FlatTrainState(BucketSchedule):
         self.seg_lr = torch.tensor(self.base_lr, dtype=torch.float32, device=dev)
         self.seg_wd = torch.tensor([hyper[id(p)][1] for p in self.params], dtype=torch.float32, device=dev)
         self.steps = 0
-        # wgrad kernels on a side stream (ops._Side): measured no gain on MI355X (YOLOv5-s 3220 -> 3134 img/s, DeepLabv3+ 394 -> 392:
-        # every kernel already fills the chip), so it is opt-in: CVHIP_ASYNC_WGRAD=1
-        import os
-        ops.enable_async_wgrad(os.environ.get("CVHIP_ASYNC_WGRAD", "0") in ("1", "2"), after_dgrad=os.environ.get("CVHIP_ASYNC_WGRAD", "0") == "2")
         # BatchNorm step counters: one multi-tensor add per step (bricks.bn_tick) instead of one tiny kernel per layer
         nbt_mods = [m for m in model.modules()
                     if isinstance(m, torch.nn.BatchNorm2d) and m.track_running_stats and m.num_batches_tracked is not None]
@@ -504,7 +500,6 @@ class FlatTrainState(BucketSchedule):
     def step_kernels(self):
         """The device work of one step (capturable): wait for the bucketed all-reduce, fused SGD+EMA, EMA of the
         BN statistics, zero the gradient arena."""
-        ops.join_side()  # side-stream wgrad kernels (ops._Side) must have landed in the gradient arena
         self.finish_allreduce()
         ema_ptr = self.ema_param.data_ptr() if self.ema_param is not None else None
         st = ops._stream()
@@ -635,7 +630,6 @@ class FlatTrainStep:
                 _, feats = m.forward_features(self.static_imgs)
                 losses = m.loss_from_features(feats, self.static_targets)
                 st.backward(losses["loss"])
-                ops.join_side()
                 if not self.eager_tail:
                     st.step_kernels()
             self.static_losses = losses
@@ -650,7 +644,6 @@ class FlatTrainStep:
         g2 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g2, pool=pool, capture_error_mode="thread_local"):
             torch.autograd.backward(self.feats, grad_tensors=self.g_feats)
-            ops.join_side()
             if not self.eager_tail:
                 st.step_kernels()
         self.g1, self.g2 = g1, g2

@@ -339,121 +339,6 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* partial,
   if (acc1) acc1[c] += (float)s2;
 }
 
-// One launch instead of rows_reduce_kernel + a finalize kernel (2 x ~4.7 us of dependent launch latency per BN layer and
-// pass: ~230 such pairs per YOLOv5-s step). Grid = (32-channel chunks, kStage2Rows row groups); every block folds its row
-// group of its chunk's 64 columns (32 sums + 32 second sums) into the scratch rows, and the LAST block of a chunk to
-// arrive (device-scope counter) reduces the chunk's scratch rows and runs the final per-channel math. Deterministic: the
-// partition and both summation orders are fixed; only WHICH block does the tail varies.
-// The counters are library-global: launches of this kernel must not overlap (they are issued on one stream).
-// MEASURED AND LEFT OFF (enable with CVHIP_FUSED_FINALIZE=1): on MI355X the device-scope release/acquire pair the
-// last-block hand-off needs (__threadfence => L2 write-back + invalidate across the 8 XCDs, whose L2s are not coherent
-// with each other) costs ~20 us per launch — YOLOv5-s 3166 -> 2811 img/s, DeepLabv3+ 392 -> 330 img/s. Two dependent
-// ~4.7 us launches are cheaper than one cross-XCD rendezvous.
-struct FinParams {
-  int mode;  // 0: BN forward statistics, 1: plain sums (out0/out1 [+= ], acc0/acc1 +=)
-  double count;
-  const float *gamma, *beta;
-  float *rmean, *rvar;
-  float momentum, eps;
-  float *mean, *invstd, *scale, *shift;
-  float *out0, *out1, *acc0, *acc1;
-  int accumulate;
-};
-__device__ unsigned int g_fin_counters[256];
-
-__global__ __launch_bounds__(256) void rows_reduce_fin_kernel(const float* __restrict__ in, int rows, int C, float* scratch, const FinParams fp) {
-  __shared__ float red[4][64];
-  __shared__ double red2[2][8][33];
-  __shared__ int s_last;
-  const int t = threadIdx.x;
-  const int j = t & 63, lane = t >> 6;
-  const int c0 = blockIdx.x * 32;
-  const int cc = c0 + (j & 31);
-  const int Wd = 2 * C;
-  const int col = (j >> 5) * C + cc;  // j < 32: first sums, j >= 32: second sums of the same 32 channels
-  const bool col_ok = cc < C;
-  const int chunk = (rows + gridDim.y - 1) / gridDim.y;
-  const int r0 = blockIdx.y * chunk;
-  const int r1 = min(rows, r0 + chunk);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (col_ok) {
-    int r = r0 + lane;
-    for (; r + 12 < r1; r += 16) {
-      a0 += in[(int64_t)r * Wd + col];
-      a1 += in[(int64_t)(r + 4) * Wd + col];
-      a2 += in[(int64_t)(r + 8) * Wd + col];
-      a3 += in[(int64_t)(r + 12) * Wd + col];
-    }
-    for (; r < r1; r += 4) a0 += in[(int64_t)r * Wd + col];
-  }
-  red[lane][j] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (lane == 0 && col_ok) scratch[(int64_t)blockIdx.y * Wd + col] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
-  __threadfence();
-  __syncthreads();
-  if (t == 0) {
-    const unsigned old = atomicAdd(&g_fin_counters[blockIdx.x], 1u);
-    const int last = (old == gridDim.y - 1);
-    if (last) g_fin_counters[blockIdx.x] = 0u;  // self-cleaning for the next launch
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  // tail: 32 channels x 8 row lanes over the gridDim.y scratch rows (written by other CUs: read past the L1)
-  const volatile float* sc = scratch;
-  const int ch = t & 31, rl = t >> 5;
-  const int c = c0 + ch;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int r = rl; r < (int)gridDim.y; r += 8) {
-      s1 += (double)sc[(int64_t)r * Wd + c];
-      s2 += (double)sc[(int64_t)r * Wd + C + c];
-    }
-  red2[0][rl][ch] = s1;
-  red2[1][rl][ch] = s2;
-  __syncthreads();
-  if (rl != 0 || c >= C) return;
-  s1 = 0.0;
-  s2 = 0.0;
-#pragma unroll
-  for (int l = 0; l < 8; ++l) {
-    s1 += red2[0][l][ch];
-    s2 += red2[1][l][ch];
-  }
-  if (fp.mode == 0) {
-    const double m = s1 / fp.count;
-    double var = s2 / fp.count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float is = (float)(1.0 / sqrt(var + (double)fp.eps));
-    const float g = fp.gamma ? fp.gamma[c] : 1.f, b = fp.beta ? fp.beta[c] : 0.f;
-    if (fp.mean) fp.mean[c] = (float)m;
-    if (fp.invstd) fp.invstd[c] = is;
-    const float scl = g * is;
-    if (fp.scale) fp.scale[c] = scl;
-    if (fp.shift) fp.shift[c] = b - (float)m * scl;
-    if (fp.rmean) fp.rmean[c] = (1.f - fp.momentum) * fp.rmean[c] + fp.momentum * (float)m;
-    if (fp.rvar) {
-      const double unb = fp.count > 1.0 ? var * fp.count / (fp.count - 1.0) : var;
-      fp.rvar[c] = (1.f - fp.momentum) * fp.rvar[c] + fp.momentum * (float)unb;
-    }
-  } else {
-    if (fp.out0) fp.out0[c] = fp.accumulate ? fp.out0[c] + (float)s1 : (float)s1;
-    if (fp.out1) fp.out1[c] = fp.accumulate ? fp.out1[c] + (float)s2 : (float)s2;
-    if (fp.acc0) fp.acc0[c] += (float)s1;
-    if (fp.acc1) fp.acc1[c] += (float)s2;
-  }
-}
-
-// launch the fused form; false when it does not apply (few rows: the plain finalize kernels need no pre-reduction)
-static bool launch_fused_finalize(const float* partial, int rows, int C, const FinParams& fp, hipStream_t s) {
-  constexpr bool on = false;   // (pre-reduction + finalize in one launch: built in round 2, measured no faster than the two launches)
-  if (!on || rows <= kStage2Rows || cdiv(C, 32) > 256) return false;
-  float* scratch = const_cast<float*>(partial) + (int64_t)rows * 2 * C;
-  hipLaunchKernelGGL(rows_reduce_fin_kernel, dim3(cdiv(C, 32), kStage2Rows), dim3(256), 0, s, partial, rows, C, scratch, fp);
-  return true;
-}
-
 // ---- elementwise passes -----------------------------------------------------------------------------
 struct EwParams {
   const h16_t *a, *y, *res;
@@ -812,15 +697,6 @@ int cvhip_bn_finalize(const float* partial, int32_t rows, int32_t C, int64_t cou
                       const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                       float* mean, float* invstd, float* scale, float* shift, void* stream) {
   if (!partial || rows <= 0 || C <= 0 || count <= 0) return CVHIP_ERR_INVALID;
-  {
-    FinParams fp{};
-    fp.mode = 0;
-    fp.count = (double)count;
-    fp.gamma = gamma; fp.beta = beta; fp.rmean = running_mean; fp.rvar = running_var;
-    fp.momentum = momentum; fp.eps = eps;
-    fp.mean = mean; fp.invstd = invstd; fp.scale = scale; fp.shift = shift;
-    if (launch_fused_finalize(partial, rows, C, fp, (hipStream_t)stream)) return check_launch("rows_reduce_fin_kernel");
-  }
   partial = prereduce(partial, &rows, 2 * C, (hipStream_t)stream);
   if (rows > kStage2Rows)
     hipLaunchKernelGGL(bn_finalize_kernel<64>, dim3(cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream, partial, rows, C,
@@ -842,12 +718,6 @@ int cvhip_bn_eval_scale_shift(int32_t C, const float* gamma, const float* beta, 
 int cvhip_bn_bwd_finalize(const float* partial, int32_t rows, int32_t C, float* dgamma, float* dbeta, float* acc_dgamma,
                           float* acc_dbeta, void* stream) {
   if (!partial || rows <= 0 || C <= 0) return CVHIP_ERR_INVALID;
-  {
-    FinParams fp{};
-    fp.mode = 1;
-    fp.out0 = dbeta; fp.out1 = dgamma; fp.acc0 = acc_dbeta; fp.acc1 = acc_dgamma; fp.accumulate = 0;
-    if (launch_fused_finalize(partial, rows, C, fp, (hipStream_t)stream)) return check_launch("rows_reduce_fin_kernel");
-  }
   partial = prereduce(partial, &rows, 2 * C, (hipStream_t)stream);
   if (rows > kStage2Rows)
     hipLaunchKernelGGL(sum_partials_kernel<64>, dim3(cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream, partial, rows, C,

@@ -57,15 +57,6 @@ struct Bwd1x1Params {
   int acc_ld;
   float *o_dgamma, *o_dbeta;
   int accumulate;
-  // "tail" (conv_plan.h IgemmCommon::tail_y): dx is the output gradient of the Conv-BN-act layer that produced x; fold that
-  // layer's BatchNorm-backward sums into ITS accumulator from the stored dx rows and its y / statistics
-  const h16_t* tail_y;
-  int tail_y_ld;
-  const float *tail_scale, *tail_shift, *tail_mean, *tail_invstd;
-  int tail_act;
-  float tail_ap;
-  double* tail_acc;
-  int tail_acc_ld;
   // XPRO instances (round 5, lazy activations): `x` is the RAW convolution output of the layer that produced this layer's input; the
   // weight gradient needs the ACTIVATED input, so the x rows are transformed on their way into the LDS tile,
   // x' = act(xs[c] * x + xh[c]) for input channels c in [x_lo, x_hi), rounded to 16 bits as the stand-alone pass would have stored them
@@ -104,13 +95,10 @@ __device__ __forceinline__ f32x8 bnact_bwd8(const f32x8& dz, const f32x8& y, con
   return o;
 }
 
-// TAIL: the tail-sums form is its own instantiation — its 2 x CB/4 per-lane partial sums are live across the whole trip loop and
-// pushed the 128 x 128 configuration to 104 spilled VGPRs (300 B/lane of scratch, 106 -> 195 us per launch) when it was a runtime flag
 // KB 256 (round 4: the 64 -> 256 / 128 -> 256 expansion layers of ResNet bottlenecks, C <= 128 = ONE input-channel slice): 128 dW
 // accumulator registers + 64 of dz / y prefetch per lane — one block per CU (launch bounds 1: up to 512 registers, AGPRs included)
-template <int KB, int CB, bool TAIL, bool XPRO = false>
+template <int KB, int CB, bool XPRO = false>
 __global__ __launch_bounds__(256, KB >= 256 ? 1 : 2) void bwd1x1_kernel(const Bwd1x1Params p) {
-  static_assert(!(TAIL && XPRO), "a lazy input has no tail form");
   constexpr int RT = 64;
   constexpr int KV = KB / 8, CV = CB / 8;
   constexpr int D_PASS = 256 / KV, D_IT = RT / D_PASS;
@@ -129,7 +117,6 @@ __global__ __launch_bounds__(256, KB >= 256 ? 1 : 2) void bwd1x1_kernel(const Bw
   unsigned char* const sW = smem;
   unsigned char* const sD = smem + W_BYTES;
   unsigned char* const sX = sD + D_BYTES;
-  float* const sT = reinterpret_cast<float*>(sX + RT * X_ROWB);  // tail: [4][CB] scale | shift | mean | invstd of channels c0 ..
 
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -279,20 +266,6 @@ __global__ __launch_bounds__(256, KB >= 256 ? 1 : 2) void bwd1x1_kernel(const Bw
     }
   };
 
-  constexpr bool tail = TAIL;
-  if (tail && t < CB) {
-    sT[t] = p.tail_scale[c0 + t];
-    sT[CB + t] = p.tail_shift[c0 + t];
-    sT[2 * CB + t] = p.tail_mean[c0 + t];
-    sT[3 * CB + t] = p.tail_invstd[c0 + t];
-  }
-  constexpr int TSN = TAIL ? NF / 2 : 1;
-  float ts1[TSN][8], ts2[TSN][8];  // this lane's share of the tail sums for channels c0 + j*32 + g*8 + e
-#pragma unroll
-  for (int j = 0; j < TSN; ++j)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ts1[j][e] = ts2[j][e] = 0.f;
-
   int tile = blockIdx.x;
   load_tile(tile);
 
@@ -356,19 +329,7 @@ __global__ __launch_bounds__(256, KB >= 256 ? 1 : 2) void bwd1x1_kernel(const Bw
 #pragma unroll
             for (int e = 0; e < 8; ++e) v.v[e] += rv.v[e];
           }
-          const uint4 packed = pack8(v);
-          *reinterpret_cast<uint4*>(drow_p + j * 32) = packed;
-          if constexpr (TAIL) {  // sums over the ROUNDED gradient, i.e. over what the tail layer's backward reads
-            const f32x8 dzr = unpack8(packed);
-            const f32x8 yv = unpack8(*reinterpret_cast<const uint4*>(p.tail_y + (int64_t)m * p.tail_y_ld + c0 + j * 32 + g * 8));
-            const float* const k = sT + j * 32 + g * 8;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float du = dzr.v[e] * act_bwd(yv.v[e] * k[e] + k[CB + e], p.tail_act, p.tail_ap);
-              ts1[j][e] += du;
-              ts2[j][e] += du * ((yv.v[e] - k[2 * CB + e]) * k[3 * CB + e]);
-            }
-          }
+          *reinterpret_cast<uint4*>(drow_p + j * 32) = pack8(v);
         }
       }
     }
@@ -395,32 +356,6 @@ __global__ __launch_bounds__(256, KB >= 256 ? 1 : 2) void bwd1x1_kernel(const Bw
         for (int b = 0; b < CF; ++b) accw[a][b] = CVHIP_MFMA_16X16X32(fd[a], fx[b], accw[a][b], 0, 0, 0);
     }
     __syncthreads();  // everybody is done with the tiles before the next trip overwrites them
-  }
-
-  // ---- tail sums: channel c0 + j*32 + g*8 + e is shared by the 16 lanes of a DPP row and by the 4 waves ----------------------------
-  if constexpr (TAIL) {
-    float* const red = reinterpret_cast<float*>(sD);  // [4 waves][CB][2]; the loop's last barrier freed the tiles
-#pragma unroll
-    for (int j = 0; j < NF / 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float u1 = row16_sum(ts1[j][e]), u2 = row16_sum(ts2[j][e]);
-        if (r == 0) {
-          const int lc = j * 32 + g * 8 + e;
-          red[(wave * CB + lc) * 2 + 0] = u1;
-          red[(wave * CB + lc) * 2 + 1] = u2;
-        }
-      }
-    __syncthreads();
-    if (t < CB) {
-      float u1 = 0.f, u2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        u1 += red[(w * CB + t) * 2 + 0];
-        u2 += red[(w * CB + t) * 2 + 1];
-      }
-      acc_add2(p.tail_acc, blockIdx.x, p.tail_acc_ld, c0 + t, u1, u2);
-    }
   }
 
   // ---- flush dW: lane holds D[k = 4g + e][c = lane & 15] per fragment -----------------------------------------------------------
@@ -474,10 +409,11 @@ int bwd1x1_fits(const cvhip_conv_desc* d) {
   return trips >= 2400 ? 1 : 0;
 }
 
-template <int KB, int CB, bool TAIL, bool XPRO = false>
+template <int KB, int CB, bool XPRO = false>
 static int launch_b1t(const Bwd1x1Params& p, int blocks, hipStream_t s) {
+  // weight tile + dz tile + x tile, and 4 * CB floats behind them that no kernel reads: the footprint the occupancy was measured with
   constexpr int LDS = CB * (KB * 2 + 16) + 64 * KB * 2 + 64 * CB * 2 + 4 * CB * (int)sizeof(float);
-  auto kern = bwd1x1_kernel<KB, CB, TAIL, XPRO>;
+  auto kern = bwd1x1_kernel<KB, CB, XPRO>;
   static bool attr_done[64] = {};  // per instantiation AND device: the attribute is a per-device property of the function
   int devid = 0;
   (void)hipGetDevice(&devid);
@@ -497,11 +433,10 @@ static int launch_b1t(const Bwd1x1Params& p, int blocks, hipStream_t s) {
 template <int KB, int CB>
 static int launch_b1(const Bwd1x1Params& p, int blocks, hipStream_t s) {
   if (p.xs) {
-    if (p.tail_y) return CVHIP_ERR_UNSUPPORTED;
-    if constexpr (KB <= 128) return launch_b1t<KB, CB, false, true>(p, blocks, s);
+    if constexpr (KB <= 128) return launch_b1t<KB, CB, true>(p, blocks, s);
     return CVHIP_ERR_UNSUPPORTED;  // (the K = 256 instances sit at their register budget)
   }
-  return p.tail_y ? launch_b1t<KB, CB, true>(p, blocks, s) : launch_b1t<KB, CB, false>(p, blocks, s);
+  return launch_b1t<KB, CB, false>(p, blocks, s);
 }
 
 int launch_bwd1x1(Bwd1x1Params& p, hipStream_t s) {
@@ -542,12 +477,12 @@ static int bwd1x1_impl(const cvhip_conv_desc* d, const void* dz0, int32_t dz0_ld
                        const void* y, const void* x, const void* w_dgrad, const float* scale, const float* shift, const float* mean,
                        const float* invstd, const float* dgamma, const float* dbeta, const double* acc, int32_t acc_ld, float* o_dgamma,
                        float* o_dbeta, int32_t accumulate, int32_t act, float act_param, const void* addend, int32_t addend_ld, void* dx,
-                       int32_t dx_ld, float* dw, void* stream, const cvhip_bn_tail* tail = nullptr, const cvhip_lazy_in* xin = nullptr,
+                       int32_t dx_ld, float* dw, void* stream, const cvhip_lazy_in* xin = nullptr,
                        const void* y1 = nullptr, int32_t y1_ld = 0) {
   if (!d || !dz0 || !y || !x || !w_dgrad || !dx || !dw) return CVHIP_ERR_INVALID;
   if (xin) {
     if (!xin->scale || !xin->shift) return CVHIP_ERR_INVALID;
-    if (tail || d->K > 128) return CVHIP_ERR_UNSUPPORTED;
+    if (d->K > 128) return CVHIP_ERR_UNSUPPORTED;
     if (xin->act != CVHIP_ACT_NONE && xin->act != CVHIP_ACT_RELU && xin->act != CVHIP_ACT_LEAKY && xin->act != CVHIP_ACT_SILU) return CVHIP_ERR_UNSUPPORTED;
   }
   if (!bwd1x1_structural(d)) return CVHIP_ERR_UNSUPPORTED;
@@ -570,7 +505,7 @@ static int bwd1x1_impl(const cvhip_conv_desc* d, const void* dz0, int32_t dz0_ld
   p.y1 = nullptr;
   p.y1_ld = 0;
   if (y1) {
-    if (k_split >= d->K || (y1_ld & 7) || (((uintptr_t)y1) & 15) || tail) return CVHIP_ERR_INVALID;
+    if (k_split >= d->K || (y1_ld & 7) || (((uintptr_t)y1) & 15)) return CVHIP_ERR_INVALID;
     p.y1 = (const h16_t*)y1;
     p.y1_ld = y1_ld;
   }
@@ -608,22 +543,6 @@ static int bwd1x1_impl(const cvhip_conv_desc* d, const void* dz0, int32_t dz0_ld
     p.x_hi = xin->c_hi > 0 ? xin->c_hi : d->C;
     if (p.x_lo < 0 || p.x_hi > d->C || p.x_lo >= p.x_hi || (p.x_lo & 7) || (p.x_hi & 7)) return CVHIP_ERR_INVALID;
   }
-  p.tail_y = nullptr;
-  if (tail) {
-    if (!tail->y || !tail->scale || !tail->shift || !tail->mean || !tail->invstd || !tail->acc || tail->acc_ld < d->C) return CVHIP_ERR_INVALID;
-    if ((tail->y_ld & 7) || (((uintptr_t)tail->y) & 15)) return CVHIP_ERR_UNSUPPORTED;
-    if (tail->act != CVHIP_ACT_NONE && tail->act != CVHIP_ACT_RELU && tail->act != CVHIP_ACT_LEAKY && tail->act != CVHIP_ACT_SILU) return CVHIP_ERR_UNSUPPORTED;
-    p.tail_y = (const h16_t*)tail->y;
-    p.tail_y_ld = tail->y_ld;
-    p.tail_scale = tail->scale;
-    p.tail_shift = tail->shift;
-    p.tail_mean = tail->mean;
-    p.tail_invstd = tail->invstd;
-    p.tail_act = tail->act;
-    p.tail_ap = tail->act_param;
-    p.tail_acc = tail->acc;
-    p.tail_acc_ld = tail->acc_ld;
-  }
   return launch_bwd1x1(p, (hipStream_t)stream);
 }
 
@@ -639,10 +558,10 @@ int cvhip_conv1x1_bwd_fused_acc(const cvhip_conv_desc* d, const void* dz0, int32
                                 const void* y, const void* x, const void* w_dgrad, const float* scale, const float* shift, const float* mean,
                                 const float* invstd, const double* acc, int32_t acc_ld, float* dgamma_out, float* dbeta_out, int32_t accumulate,
                                 int32_t act, float act_param, const void* addend, int32_t addend_ld, void* dx, int32_t dx_ld, float* dw,
-                                const cvhip_bn_tail* tail, void* stream) {
+                                void* stream) {
   if (!acc && mean) return CVHIP_ERR_INVALID;
   return bwd1x1_impl(d, dz0, dz0_ld, dz1, dz1_ld, k_split, y, x, w_dgrad, scale, shift, mean, invstd, nullptr, nullptr, acc, acc_ld, dgamma_out,
-                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream, tail);
+                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream);
 }
 
 int cvhip_conv1x1_bwd_fused_split(const cvhip_conv_desc* d, const void* dz0, int32_t dz0_ld, const void* dz1, int32_t dz1_ld, int32_t k_split,
@@ -653,7 +572,7 @@ int cvhip_conv1x1_bwd_fused_split(const cvhip_conv_desc* d, const void* dz0, int
   if (!acc && mean) return CVHIP_ERR_INVALID;
   if (!y1) return CVHIP_ERR_INVALID;
   return bwd1x1_impl(d, dz0, dz0_ld, dz1, dz1_ld, k_split, y, x, w_dgrad, scale, shift, mean, invstd, nullptr, nullptr, acc, acc_ld, dgamma_out,
-                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream, nullptr, xin, y1, y1_ld);
+                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream, xin, y1, y1_ld);
 }
 
 int cvhip_conv1x1_bwd_fused_lazy(const cvhip_conv_desc* d, const void* dz0, int32_t dz0_ld, const void* dz1, int32_t dz1_ld, int32_t k_split,
@@ -664,7 +583,7 @@ int cvhip_conv1x1_bwd_fused_lazy(const cvhip_conv_desc* d, const void* dz0, int3
   if (!acc && mean) return CVHIP_ERR_INVALID;
   if (!xin) return CVHIP_ERR_INVALID;
   return bwd1x1_impl(d, dz0, dz0_ld, dz1, dz1_ld, k_split, y, x_raw, w_dgrad, scale, shift, mean, invstd, nullptr, nullptr, acc, acc_ld, dgamma_out,
-                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream, nullptr, xin);
+                     dbeta_out, accumulate, act, act_param, addend, addend_ld, dx, dx_ld, dw, stream, xin);
 }
 
 }  // extern "C"

@@ -28,8 +28,7 @@ constexpr int kS1MaxLds = 72 * 1024;   // weight tile incl. row padding (+ 1 KB 
 constexpr int kS1MaxBlocks = 512;      // persistent grid: 2 blocks per CU
 constexpr int kS1MinTiles = 192;       // below this the grid cannot cover the chip: the general kernel's smaller tiles win
 
-// STATS: 0 = none, 1 = BatchNorm sums of the outputs (fprop), 2 = "tail" (dgrad; conv_plan.h IgemmCommon::tail_y): BatchNorm-BACKWARD
-// sums of the layer whose output gradient this launch produces, from the stored dz and that layer's y / statistics
+// STATS: 0 = none, 1 = BatchNorm sums of the outputs (fprop)
 
 // activation of 8 / 4 values with ONE switch (a switch per element multiplied the unrolled epilogue's code size and pushed the
 // 256-wide streaming kernel's accumulators into scratch)
@@ -143,23 +142,17 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const IgemmKernA
     }
   }
   float* const sbias = reinterpret_cast<float*>(smem + BN * brow);  // [BN] fp32 behind the weight tile
-  const float* const stail = sbias + BN;                            // [4][BN]: scale | shift | mean | invstd of the tail layer
+  const float* const sepi = sbias + BN;                             // EPI: [2][BN] scale | shift of the output channels
   if (p.bias && t < BN) sbias[t] = (n0 + t < p.bias_n) ? p.bias[n0 + t] : 0.f;
-  // fused epilogue: the constants share the tail rows
   static_assert(!EPI || STATS == 0, "the fused epilogue excludes BatchNorm sums");
   if (EPI && t < BN) {
     const int n = n0 + t < p.Nout ? n0 + t : p.Nout - 1;
     sbias[BN + t] = p.ep_scale ? p.ep_scale[n] : 1.f;
     sbias[2 * BN + t] = p.ep_scale ? p.ep_shift[n] : 0.f;
   }
-  if (STATS == 2 && t < BN) {
-    const int n = n0 + t < p.Nout ? n0 + t : p.Nout - 1;
-    sbias[BN + t] = p.tail_scale[n];
-    sbias[2 * BN + t] = p.tail_shift[n];
-    sbias[3 * BN + t] = p.tail_mean[n];
-    sbias[4 * BN + t] = p.tail_invstd[n];
-  }
-  float* const spro = sbias + 5 * BN;  // PRO: [2][cin_pad] scale | shift of the input channels, behind the tail rows
+  // PRO: [2][cin_pad] scale | shift of the input channels, 5 * BN floats behind the bias row (the LDS layout the kernel was measured
+  // with; rows 3 and 4 of that block are unused)
+  float* const spro = sbias + 5 * BN;
   if constexpr (PRO) {
     for (int c = t; c < cin_pad; c += 256) {
       const bool in = c >= p.pro_lo && c < p.pro_hi && c < Cin;
@@ -238,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const IgemmKernA
         if constexpr (EPI) {
           const int cl8 = j * 32 + g * 8;
 #pragma unroll
-          for (int q = 0; q < 8; ++q) v.v[q] = v.v[q] * stail[cl8 + q] + stail[BN + cl8 + q];
+          for (int q = 0; q < 8; ++q) v.v[q] = v.v[q] * sepi[cl8 + q] + sepi[BN + cl8 + q];
           if (p.res && p.res_pre && m < M) {  // residual before the activation (ResNet bottleneck tail)
             const h16_t* rrow = p.res + (int64_t)m * p.res_ld + ch0;
 #pragma unroll
@@ -257,27 +250,6 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const IgemmKernA
 #pragma unroll
             for (int q = 0; q < 8; ++q)
               if (ch0 + q < p.Nout) v.v[q] += (float)rrow[q];
-          }
-        }
-        if constexpr (STATS == 2) {
-          if (m < M) {  // tail sums over the ROUNDED dz (what the tail layer's backward reads); the host guarantees the vector path
-            const uint4 packed = pack8(v);
-            const f32x8 dzr = unpack8(packed);
-            const f32x8 yv = unpack8(*reinterpret_cast<const uint4*>(p.tail_y + (int64_t)m * p.tail_y_ld + ch0));
-            const int cl8 = j * 32 + g * 8;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              const float sc = stail[cl8 + q], sh = stail[BN + cl8 + q], mu = stail[2 * BN + cl8 + q], is = stail[3 * BN + cl8 + q];
-              const float du = dzr.v[q] * act_bwd(yv.v[q] * sc + sh, p.tail_act, p.tail_ap);
-              const float dx = du * ((yv.v[q] - mu) * is);
-              if (q < 4) {
-                s1[2 * j][q] += du;
-                s2[2 * j][q] += dx;
-              } else {
-                s1[2 * j + 1][q - 4] += du;
-                s2[2 * j + 1][q - 4] += dx;
-              }
-            }
           }
         }
         if (m < M) {
@@ -421,7 +393,7 @@ static bool s1x1_structural(const IgemmParams& p) {
          c.out_oh == 0 && c.out_ow == 0 && c.OHi == p.OH && c.OWi == p.OW && p.IH == p.OH && p.IW == p.OW && (p.x_ld & 7) == 0;
 }
 
-// LDS bytes of a launch: weight tile + bias + the tail layer's 4 constant rows (+ the prologue's scale | shift rows)
+// LDS bytes of a launch: weight tile + bias + 4 constant rows (the epilogue's scale | shift, two unused) (+ the prologue's scale | shift rows)
 static int s1x1_lds(int bn, int cin_pad, bool pro) {
   int lds = bn * (cin_pad * 2 + 16) + 5 * bn * (int)sizeof(float) + (pro ? 2 * cin_pad * (int)sizeof(float) : 0);
   if (lds < 4 * bn * 2 * (int)sizeof(float)) lds = 4 * bn * 2 * (int)sizeof(float);
@@ -479,7 +451,7 @@ int try_launch_stream1x1(const IgemmParams& p, hipStream_t stream) {
     return CVHIP_ERR_INVALID;
   if (p.pro_scale) {
     // lazy input: BN scale / shift + activation of the producing layer applied on load (training forms: raw output, optional BN sums)
-    if (p.tail_y || p.ep_scale || p.ep_act != CVHIP_ACT_NONE || p.res || !stream1x1_prologue_ok(p, p.stats != nullptr)) return CVHIP_ERR_UNSUPPORTED;
+    if (p.ep_scale || p.ep_act != CVHIP_ACT_NONE || p.res || !stream1x1_prologue_ok(p, p.stats != nullptr)) return CVHIP_ERR_UNSUPPORTED;
     if (p.pro_lo < 0 || p.pro_hi > p.Cin || p.pro_lo >= p.pro_hi || (p.pro_lo & 7) || (p.pro_hi & 7)) return CVHIP_ERR_INVALID;
     if (p.stats) {
       if (nf == 2) return launch_s1<2, 1, false, true>(p, blocks, ntiles, stream);
@@ -489,11 +461,6 @@ int try_launch_stream1x1(const IgemmParams& p, hipStream_t stream) {
     if (nf == 2) return launch_s1<2, 0, false, true>(p, blocks, ntiles, stream);
     if (nf == 4) return launch_s1<4, 0, false, true>(p, blocks, ntiles, stream);
     return launch_s1<8, 0, false, true>(p, blocks, ntiles, stream);
-  }
-  if (p.stats && p.tail_y) {
-    if (nf == 2) return launch_s1<2, 2>(p, blocks, ntiles, stream);
-    if (nf == 4) return launch_s1<4, 2>(p, blocks, ntiles, stream);
-    return launch_s1<8, 2>(p, blocks, ntiles, stream);
   }
   if (p.stats) {
     if (nf == 2) return launch_s1<2, 1>(p, blocks, ntiles, stream);

@@ -732,7 +732,7 @@ static bool band_plan(const IgemmParams& p, BandPlan* pl) {
   const IgemmClass& c = p.cls[0];
   if (p.in_sh == 2 && !(c.dh0 == -1 && c.dw0 == -1 && c.dh_step == 1 && c.dw_step == 1)) return false;   // stride 2: 3x3, padding 1, dilation 1
   if (c.TR != 3 || c.TS != 3 || c.out_oh != 0 || c.out_ow != 0 || c.OHi != p.OH || c.OWi != p.OW || c.M <= 0) return false;
-  if (p.pro_scale || p.z_out || p.y2 || p.x_image || p.tail_y) return false;
+  if (p.pro_scale || p.z_out || p.y2 || p.x_image) return false;
   if ((p.ep_scale == nullptr) != (p.ep_shift == nullptr)) return false;
   if ((p.bias || p.ep_scale || p.ep_act != CVHIP_ACT_NONE) && p.stats) return false;   // (BN sums are those of the raw accumulators: never with an epilogue)
   if (p.stats && !p.stats_acc) return false;

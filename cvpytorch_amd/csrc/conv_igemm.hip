@@ -33,8 +33,8 @@
 namespace cvhip {
 
 // (The register-staged v1 kernel of round 1 and the measured-and-rejected launch forms — 64-deep ring slots, 8-wave blocks, wave
-// specialisation, chunk-major K order, the ablation instances — left the product library in round 6: git history and DESIGN.md 4.0 keep
-// their measurements.)
+// specialisation, chunk-major K order, the ablation instances — left the product library: git history and DESIGN.md 4.0 keep their
+// measurements.)
 
 // =====================================================================================================
 // v2: the same implicit GEMM with LDS-DMA staging (global_load_lds_dwordx4: HBM/L2 -> LDS without a VGPR hop and
@@ -72,49 +72,22 @@ __device__ __forceinline__ void wait_vmcnt() {
   else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
 }
 
-// ABL: profiling ablation (CVHIP_IGEMM_ABLATE): 0 = the kernel, 1 = staging only (no LDS reads / MFMA), 2 = compute only
-// BK : reduction depth per ring slot / barrier. 32: LDS rows of 64 B, a DMA instruction covers 16 rows x 64 B (half cache lines).
-//      64: LDS rows of 128 B, a DMA instruction covers 8 rows x 128 B = FULL 128-byte lines of the NHWC channel axis (when
-//      Cin >= 64), half the barriers / tap decodes / counted waits per MFMA (cdna_hip_programming.md §5: "x through LDS in
-//      full 128-B lines", BK 32 -> 64). The 16-B slots of a 128-B row are XOR-swizzled by (row >> 1) & 7 — conflict-free for
-//      the 16-lane groups of ds_read_b128 — on the DMA SOURCE side and on the fragment reads (rule 21).
-// FAST: Cin % BK == 0, so a K step lies inside ONE tap and its channel offset advances by BK: the per-row source pointers are
+// FAST: Cin % 32 == 0, so a K step lies inside ONE tap and its channel offset advances by 32: the per-row source pointers are
 //      kept in registers, bumped by one 64-bit add per K step and re-derived (halo test, pixel address) only when the tap changes —
-//      every Cin / BK steps, under a wave-uniform branch. The general path re-decodes (tap, channel) and re-tests the halo for every
+//      every Cin / 32 steps, under a wave-uniform branch. The general path re-decodes (tap, channel) and re-tests the halo for every
 //      row at every K step: ~110 VALU instructions and four divergent branches per step, which made ADDRESS GENERATION, not the
-//      DMA rate, the cost of staging (profiles/r01_igemm_ablation.log: staging-only 146 us vs 48 us of pure MFMA; halving the
-//      steps with BK 64 doubled the rows per step and changed nothing: profiles/r02_ab_bwd1x1_bk64.log).
+//      DMA rate, the cost of staging (profiles/r01_igemm_ablation.log: staging-only 146 us vs 48 us of pure MFMA).
 // A register-double-buffered variant (fragments of tile kt+1 read while tile kt is multiplied, asm-issued ds_read_b128 with one
 // explicit lgkmcnt wait per step) was built and measured in round 2: 8-13 % SLOWER per kernel (profiles/r02_igemm_ablation.log) and
 // removed — the step is not bound by the latency of its own fragment reads.
-// NW : waves per block. 4: one wave per SIMD and block; 8 (512 threads): two — the same block tile with HALF the wave tile, so a block
-//      alone on its CU still has a second wave per SIMD to issue MFMAs while the first one sits in its DMA-issue / fragment-read /
-//      barrier phase (profiles/r03_ceilings_probe.log: neither the LDS read rate nor the L2->LDS path is the limit of the 4-wave
-//      form; its in-order waves are).
 // (occupancy bound = the blocks per CU the LDS ring allows, at most 4: keeps the register allocation from dropping a resident block —
 // the 256x64 two-slot configuration sits exactly on the 128-VGPR step)
-constexpr int igemm_lds_bytes(int BM, int BN, int BK, int NST, int LW) {
-  const int rpt = LW * (1024 / (BK * 2));
-  return NST * (BM + (BN < rpt ? rpt : BN)) * BK * 2;
-}
-constexpr int igemm_min_waves(int BM, int BN, int BK, int NST, int NW, int LW, int acc_regs) {
-  const int blocks = (160 * 1024) / igemm_lds_bytes(BM, BN, BK, NST, LW);
+constexpr int igemm_lds_bytes(int BM, int BN, int NST) { return NST * (BM + (BN < 64 ? 64 : BN)) * 64; }
+constexpr int igemm_min_waves(int BM, int BN, int NST, int acc_regs) {
+  const int blocks = (160 * 1024) / igemm_lds_bytes(BM, BN, NST);
   const int cap = acc_regs >= 128 ? 2 : 4;  // a 128-register accumulator tile leaves room for two waves per SIMD at most
-  return (blocks < 1 ? 1 : blocks > cap ? cap : blocks) * (NW / 4);
+  return blocks < 1 ? 1 : blocks > cap ? cap : blocks;
 }
-// WS : wave specialisation (NW = 8, FAST, 3-deep ring). Waves 0-3 are CONSUMERS: fragment reads + MFMA only, one per SIMD, the whole
-//      block tile between them (128x64 each for 256x128); waves 4-7 are LOADERS: they issue every LDS DMA of the ring and wait for
-//      it, nothing else. Wave w and wave w + 4 share a SIMD (workgroup waves are dealt to the SIMDs cyclically), so every SIMD runs
-//      one MFMA stream that never stops to compute addresses / issue DMAs / wait for its own loads, beside one VMEM stream that never
-//      competes for the matrix pipe. One s_barrier per ring slot couples the two roles (loaders arrive once the next slot has
-//      landed, consumers once they are done with the current one). Why: profiles/r03_igemm_ablation.log — in the symmetric form
-//      staging-only takes 126 us, fragment reads + MFMA only 115 us, both together 181 us: the two halves barely overlap because
-//      the same in-order waves do both and the blocks of a CU fall into step.
-// ORD: K-step order of FAST staging. 0: tap-major (all channel chunks of a tap, then the next tap) — a pixel row's cache lines are
-//      touched again only Cin / BK steps later, by the next tap. 1: CHUNK-major (all taps of a channel chunk, then the next chunk):
-//      consecutive steps read the same BK-channel segment of (almost) the same pixel rows, shifted by one tap, so the re-reads hit
-//      in L2 instead of going back to the Infinity Cache (profiles/r03_igemm_ablation.log: the pixel-tile DMA alone ran at the
-//      fabric's ~10 TB/s, 17 B/clk/CU, against 30-50 B/clk/CU for the same pattern from an L2-resident window).
 
 // activation of 8 / 4 values with ONE switch (a switch per element multiplied the unrolled epilogue's code size and pushed the
 // 256-wide streaming kernel's accumulators into scratch)
@@ -146,18 +119,15 @@ __device__ __forceinline__ void ig_act_vec(float (&v)[NV], int act, float ap) {
 }
 
 // EPI: fused-epilogue instance (out = act((acc + bias) * ep_scale + ep_shift)); the default instances carry none of its code
-template <int BM, int BN, int WM, int WN, int ABL = 0, int NST = 3, int BK = 32, bool FAST = false, int NW = 4, bool WS = false, int ORD = 0, bool EPI = false>
-__global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, NW, NW, WM * WN / 64)) void igemm_dma_kernel(const IgemmKernArgs p) {
+template <int BM, int BN, int WM, int WN, int NST = 3, bool FAST = false, bool EPI = false>
+__global__ __launch_bounds__(256, igemm_min_waves(BM, BN, NST, WM * WN / 64)) void igemm_dma_kernel(const IgemmKernArgs p) {
   constexpr int WAVES_N = BN / WN;
   constexpr int WAVES_M = BM / WM;
-  constexpr int CW = WS ? 4 : NW;       // waves that compute
-  constexpr int LW = WS ? NW - 4 : NW;  // waves that stage
-  static_assert(!WS || (NW == 8 && FAST && NST == 3), "wave specialisation: 4 consumers + 4 loaders on the FAST 3-deep ring");
-  static_assert(WAVES_M * WAVES_N == CW, "one wave tile per computing wave");
-  static_assert(BK == 32 || BK == 64, "reduction depth per stage");
+  static_assert(WAVES_M * WAVES_N == 4, "one wave tile per wave");
   constexpr int MF = WM / 16, NF = WN / 16;
-  constexpr int RPI = 1024 / (BK * 2);  // rows per DMA instruction (1 KiB): 16 (BK 32) / 8 (BK 64)
-  constexpr int RPT = LW * RPI;         // rows per pass of the staging waves: 64 / 32 (4 waves)
+  constexpr int BK = 32;                // reduction depth per ring slot / barrier
+  constexpr int RPI = 1024 / (BK * 2);  // rows per DMA instruction (1 KiB): 16
+  constexpr int RPT = 4 * RPI;          // rows per pass of the 4 waves: 64
   constexpr int ROWB = BK * 2;          // LDS row bytes
   constexpr int A_IT = BM / RPT;
   constexpr int B_ROWS = BN < RPT ? RPT : BN;  // B tile padded so all 4 waves issue the same DMA count
@@ -171,11 +141,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const bool consumer = !WS || wave < 4;           // wave-uniform roles
-  const int cwave = WS ? (wave & 3) : wave;        // index among the computing waves (loaders: unused)
-  const int swave = WS ? (wave & 3) : wave;        // index among the staging waves (consumers: unused)
-  const int st_t = WS ? (t & 255) : t;             // thread index among the staging threads
-  const int wm = cwave / WAVES_N, wn = cwave % WAVES_N;
+  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
   const int lt = xcd_remap(blockIdx.x, p.total_tiles);
   int ci = 0, local;
@@ -225,11 +191,11 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   // A class WITHOUT taps (1x1 stride-2 dgrad: three of the four pixel parities — the ResNet projection shortcuts) has nothing to multiply:
   // its pixels are the addend, or zero. Copy them row by row (16 bytes per lane, whole pixel rows) and leave: no accumulators, no LDS
   // tile, no barriers (round 6: DeepLabv3+ 256 -> 512 k1 s2 @128x256, three quarters of whose tiles are of this kind).
-  if constexpr (!EPI && ABL == 0) {
-    if (nk == 0 && p.staged_epilogue && !p.bias && !p.stats && !p.tail_y && (p.Nout & 7) == 0 && (p.y_ld & 7) == 0 && ((((uintptr_t)p.y) & 15) == 0) &&
+  if constexpr (!EPI) {
+    if (nk == 0 && p.staged_epilogue && !p.bias && !p.stats && (p.Nout & 7) == 0 && (p.y_ld & 7) == 0 && ((((uintptr_t)p.y) & 15) == 0) &&
         (!p.res || ((p.res_ld & 7) == 0 && ((((uintptr_t)p.res) & 15) == 0)))) {
       constexpr int CPR0 = BN / 8;
-      for (int idx = t; idx < BM * CPR0; idx += NW * 64) {
+      for (int idx = t; idx < BM * CPR0; idx += 256) {
         const int row = idx / CPR0, ch = idx - row * CPR0;
         const int m = m0 + row;
         if (m >= M || n0 + ch * 8 >= p.Nout) continue;
@@ -247,7 +213,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   }
 
   // staging geometry: this thread's row inside a 4-wave pass and its physical 16-B slot inside the LDS row
-  const int srow = BK == 32 ? (st_t >> 2) : (swave * 8 + (lane >> 3));
+  const int srow = t >> 2;
   int ih0[A_IT], iw0[A_IT], pbase[A_IT];
 #pragma unroll
   for (int i = 0; i < A_IT; ++i) {
@@ -271,11 +237,10 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   const h16_t* __restrict__ wbase = p.w + cl.w_off;
   const h16_t* const zero = reinterpret_cast<const h16_t*>(g_zero_page);
 
-  // BK 32: physical slot (t&3) of a 64-B row must hold LOGICAL K-slot (t&3)^g(row>>2)
-  // BK 64: physical slot (lane&7) of a 128-B row must hold LOGICAL K-slot (lane&7) ^ ((row>>1)&7), row = i*32 + wave*8 + (lane>>3)
-  const int lslot = BK == 32 ? ((st_t & 3) ^ ((0x78 >> (2 * ((st_t >> 4) & 3))) & 3)) : ((lane & 7) ^ (((swave & 1) << 2) | (lane >> 4)));
-  // fragment reads: lane (r = lane&15, g = lane>>4) reads logical slot 4*ks + g of row base + r
-  const int swz_r = BK == 32 ? ((lane >> 4) ^ ((0x78 >> (2 * ((lane >> 2) & 3))) & 3)) : ((lane >> 1) & 7);
+  // physical slot (t&3) of a 64-B row must hold LOGICAL K-slot (t&3)^g(row>>2)
+  const int lslot = (t & 3) ^ ((0x78 >> (2 * ((t >> 4) & 3))) & 3);
+  // fragment reads: lane (r = lane&15, g = lane>>4) reads logical slot g of row base + r
+  const int swz_r = (lane >> 4) ^ ((0x78 >> (2 * ((lane >> 2) & 3))) & 3);
 
   auto stage = [&](int kt, int st) {
     const unsigned k = (unsigned)(kt * BK + lslot * 8);
@@ -292,7 +257,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
       const int ih = ih0[i] + dh, iw = iw0[i] + dw;
       const bool ok = tap_ok && (unsigned)ih < (unsigned)p.IH && (unsigned)iw < (unsigned)p.IW;
       const h16_t* src = ok ? (p.x + ((int64_t)(pbase[i] + ih * p.IW + iw) * p.x_ld + c0)) : zero;
-      CVHIP_GLDS16(src, sA + (i * RPT + swave * RPI) * ROWB);
+      CVHIP_GLDS16(src, sA + (i * RPT + wave * RPI) * ROWB);
     }
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
@@ -300,7 +265,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
       const int n = n0 + row;
       const bool ok = row < BN && n < p.Nout && (int)k < Ktot;
       const h16_t* src = ok ? (wbase + ((int64_t)n * Ktot + k)) : zero;
-      CVHIP_GLDS16(src, sB + (i * RPT + swave * RPI) * ROWB);
+      CVHIP_GLDS16(src, sB + (i * RPT + wave * RPI) * ROWB);
     }
   };
 
@@ -318,55 +283,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) aptr[i] = zero;
   }
-  // chunk-major order (ORD 1): per staged row the address of its tap-(0,0) pixel and one validity bit per tap; a step's source is
-  // base + (wave-uniform tap offset + chunk offset) or the zero page
-  unsigned amask[A_IT];
-  int o_t = 0, o_c = 0;
-  const int ntaps = TR * TS;
-  if constexpr (FAST && ORD == 1) {
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-      unsigned mk = 0;
-      for (int tr = 0, b = 0; tr < TR; ++tr)
-        for (int ts = 0; ts < TS; ++ts, ++b) {
-          const int ih = ih0[i] + tr * cl.dh_step, iw = iw0[i] + ts * cl.dw_step;
-          mk |= (((unsigned)ih < (unsigned)p.IH && (unsigned)iw < (unsigned)p.IW) ? 1u : 0u) << b;
-        }
-      amask[i] = mk;
-      // (rows past M carry ih0 = -2^28: no valid tap, the base below is never dereferenced)
-      aptr[i] = p.x + ((int64_t)(pbase[i] + ih0[i] * p.IW + iw0[i]) * p.x_ld + lslot * 8);
-    }
-  }
   auto stage_fast = [&](int st) {
-    if constexpr (ORD == 1) {
-      const int64_t toff = ((int64_t)(f_tr * cl.dh_step) * p.IW + f_ts * cl.dw_step) * p.x_ld + o_c;  // wave-uniform
-      const unsigned bit = 1u << o_t;
-      unsigned char* const sA1 = smem + st * ST_BYTES;
-      unsigned char* const sB1 = sA1 + A_BYTES;
-      if (ABL != 5) {
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i) {
-          const h16_t* src = (amask[i] & bit) ? aptr[i] + toff : zero + lslot * 8;
-          CVHIP_GLDS16(src, sA1 + (i * RPT + swave * RPI) * ROWB);
-        }
-      }
-      const int boff = o_t * Cin + o_c;  // weight column of (tap, chunk)
-      if (ABL != 4) {
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) CVHIP_GLDS16(bptr[i] + boff, sB1 + (i * RPT + swave * RPI) * ROWB);
-      }
-      ++o_t;
-      if (++f_ts == TS) {
-        f_ts = 0;
-        ++f_tr;
-      }
-      if (o_t == ntaps) {
-        o_t = 0;
-        f_tr = f_ts = 0;
-        o_c += BK;
-      }
-      return;
-    }
     if (f_c == 0) {  // first K step of a tap: halo test + pixel address, once per Cin / BK steps
       const int dh = f_tr * cl.dh_step, dw = f_ts * cl.dw_step;
 #pragma unroll
@@ -379,32 +296,23 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
     }
     unsigned char* const sA = smem + st * ST_BYTES;
     unsigned char* const sB = sA + A_BYTES;
-    // ABL 3 (experiment, wrong results): pixel rows are fetched for 2 of 9 taps only — the DMA volume a patch-in-LDS layout with
-    // tap reuse would have; measures how much of the kernel's time is the issue cost of the A-tile DMA pieces
-    const bool a_live = (ABL != 3 || ((f_tr * TS + f_ts) % 6 == 0)) && ABL != 5;  // ABL 5: weight tile only
     if (f_c + BK > Cin) {
       // (wave-uniform, rare) the LAST step of a single-tap plan whose channel count is not a multiple of the step (round 6: the
       // 560 -> 512 1x1 of DeepLabv3+'s decoder ran the general staging path): the 16-byte slots past the last channel come from the
       // zero page, pixel tile and weight tile alike. (No early return: it sent the lambda's by-reference state to scratch memory.)
       const bool dead = f_c + lslot * 8 >= Cin;
-      if (a_live) {
 #pragma unroll
-        for (int i = 0; i < A_IT; ++i) CVHIP_GLDS16(dead ? zero : aptr[i], sA + (i * RPT + swave * RPI) * ROWB);
-      }
+      for (int i = 0; i < A_IT; ++i) CVHIP_GLDS16(dead ? zero : aptr[i], sA + (i * RPT + wave * RPI) * ROWB);
 #pragma unroll
-      for (int i = 0; i < B_IT; ++i) {
-        if (ABL != 4) CVHIP_GLDS16(dead ? zero : bptr[i], sB + (i * RPT + swave * RPI) * ROWB);
-      }
+      for (int i = 0; i < B_IT; ++i) CVHIP_GLDS16(dead ? zero : bptr[i], sB + (i * RPT + wave * RPI) * ROWB);
     } else {
-      if (a_live) {
 #pragma unroll
-        for (int i = 0; i < A_IT; ++i) CVHIP_GLDS16(aptr[i], sA + (i * RPT + swave * RPI) * ROWB);
-      }
+      for (int i = 0; i < A_IT; ++i) CVHIP_GLDS16(aptr[i], sA + (i * RPT + wave * RPI) * ROWB);
 #pragma unroll
       for (int i = 0; i < A_IT; ++i) aptr[i] += BK;
 #pragma unroll
       for (int i = 0; i < B_IT; ++i) {
-        if (ABL != 4) CVHIP_GLDS16(bptr[i], sB + (i * RPT + swave * RPI) * ROWB);  // ABL 4: pixel tile only
+        CVHIP_GLDS16(bptr[i], sB + (i * RPT + wave * RPI) * ROWB);
         bptr[i] += BK;
       }
     }
@@ -429,91 +337,31 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   auto compute = [&](int st) __attribute__((always_inline)) {
     const unsigned char* const sA = smem + st * ST_BYTES;
     const unsigned char* const sB = sA + A_BYTES;
-    if constexpr (WS && BK == 64) {
-      // all fragment reads of the slot first: the second half's reads complete behind the first half's MFMAs (a consumer wave is
-      // alone on its SIMD's matrix pipe: nobody else hides its read latency)
-      h16x8 xa[2][MF], wb[2][NF];
+    h16x8 xa[MF], wb[NF];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int slot = (4 * ks + (lane >> 4)) ^ swz_r;
+    for (int b = 0; b < MF; ++b) xa[b] = *reinterpret_cast<const h16x8*>(sA + (a_row + b * 16) * ROWB + swz_r * 16);
 #pragma unroll
-        for (int a = 0; a < NF; ++a) wb[ks][a] = *reinterpret_cast<const h16x8*>(sB + (b_row + a * 16) * ROWB + slot * 16);
+    for (int a = 0; a < NF; ++a) wb[a] = *reinterpret_cast<const h16x8*>(sB + (b_row + a * 16) * ROWB + swz_r * 16);
 #pragma unroll
-        for (int b = 0; b < MF; ++b) xa[ks][b] = *reinterpret_cast<const h16x8*>(sA + (a_row + b * 16) * ROWB + slot * 16);
-      }
+    for (int a = 0; a < NF; ++a)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int a = 0; a < NF; ++a)
-#pragma unroll
-          for (int b = 0; b < MF; ++b)
-            acc[a][b] = CVHIP_MFMA_16X16X32(wb[ks][a], xa[ks][b], acc[a][b], 0, 0, 0);
-      return;
-    }
-#pragma unroll
-    for (int ks = 0; ks < BK / 32; ++ks) {
-      const int slot = BK == 32 ? swz_r : ((4 * ks + (lane >> 4)) ^ swz_r);
-      h16x8 xa[MF], wb[NF];
-#pragma unroll
-      for (int b = 0; b < MF; ++b) xa[b] = *reinterpret_cast<const h16x8*>(sA + (a_row + b * 16) * ROWB + slot * 16);
-#pragma unroll
-      for (int a = 0; a < NF; ++a) wb[a] = *reinterpret_cast<const h16x8*>(sB + (b_row + a * 16) * ROWB + slot * 16);
-#pragma unroll
-      for (int a = 0; a < NF; ++a)
-#pragma unroll
-        for (int b = 0; b < MF; ++b)
-          acc[a][b] = CVHIP_MFMA_16X16X32(wb[a], xa[b], acc[a][b], 0, 0, 0);
-    }
+      for (int b = 0; b < MF; ++b)
+        acc[a][b] = CVHIP_MFMA_16X16X32(wb[a], xa[b], acc[a][b], 0, 0, 0);
   };
 
-  if constexpr (WS) {
-    if (!consumer) {
-      // LOADER: keeps two ring slots in flight; arrives at barrier #kt once slot kt has landed, then refills the slot the
-      // consumers finished with before they arrived there (slot kt - 1 = kt + 2 mod 3)
-      if (ABL != 2) {
-        if (nk > 0) stage_fast(0);
-        if (nk > 1) stage_fast(1);
-      }
-      int st_nxt2 = 2;
-      for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) wait_vmcnt<PER>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (ABL != 2 && kt + 2 < nk) stage_fast(st_nxt2);
-        st_nxt2 = st_nxt2 == NST - 1 ? 0 : st_nxt2 + 1;
-      }
-    } else {
-      // CONSUMER: one barrier per ring slot, then nothing but fragment reads and MFMAs
-      int st_cur = 0;
-      for (int kt = 0; kt < nk; ++kt) {
-        __builtin_amdgcn_s_barrier();
-        if (ABL != 1) compute(st_cur);
-        st_cur = st_cur == NST - 1 ? 0 : st_cur + 1;
-      }
-    }
-  } else if constexpr (FAST && NST == 3) {
+  if constexpr (FAST && NST == 3) {
     // no DMA is issued past the last tile (the running weight pointers would leave the array), so the last step waits for
     // everything instead of "all but the next tile"
     // a class without taps (1x1 stride-2 dgrad: three of the four pixel parities) has nk == 0: nothing to stage, zeros are stored
-    if (ABL != 2) {
-      if (nk > 0) stage_fast(0);
-      if (nk > 1) stage_fast(1);
-    }
+    if (nk > 0) stage_fast(0);
+    if (nk > 1) stage_fast(1);
     int st_cur = 0, st_nxt2 = 2;
     for (int kt = 0; kt < nk; ++kt) {
-      if (ABL == 4) {
-        if (kt + 1 < nk) wait_vmcnt<A_IT>();
-        else wait_vmcnt<0>();
-      } else if (ABL == 5) {
-        if (kt + 1 < nk) wait_vmcnt<B_IT>();
-        else wait_vmcnt<0>();
-      } else {
-        if (kt + 1 < nk) wait_vmcnt<PER>();
-        else wait_vmcnt<0>();
-      }
+      if (kt + 1 < nk) wait_vmcnt<PER>();
+      else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
-      if (ABL != 2 && kt + 2 < nk) stage_fast(st_nxt2);
-      if (ABL != 1 && ABL != 4 && ABL != 5) compute(st_cur);
+      if (kt + 2 < nk) stage_fast(st_nxt2);
+      compute(st_cur);
       st_cur = st_cur == NST - 1 ? 0 : st_cur + 1;
       st_nxt2 = st_nxt2 == NST - 1 ? 0 : st_nxt2 + 1;
     }
@@ -534,8 +382,8 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
       wait_vmcnt<PER>();
       // ... and after the barrier everybody's have; it also proves all waves finished reading ring slot (kt+2)%3
       __builtin_amdgcn_s_barrier();
-      if (ABL != 2) stage(kt + 2, st_nxt2);  // past-the-end tiles decode to all-masked lanes (zero page): DMA counts stay uniform
-      if (ABL != 1) compute(st_cur);
+      stage(kt + 2, st_nxt2);  // past-the-end tiles decode to all-masked lanes (zero page): DMA counts stay uniform
+      compute(st_cur);
       st_cur = st_cur == NST - 1 ? 0 : st_cur + 1;
       st_nxt2 = st_nxt2 == NST - 1 ? 0 : st_nxt2 + 1;
     }
@@ -545,21 +393,20 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // tile kt landed everywhere; everybody finished reading slot (kt+1)&1 (= tile kt-1)
-      if (ABL != 2) stage(kt + 1, (kt + 1) & 1);
-      if (ABL != 1) compute(kt & 1);
+      stage(kt + 1, (kt + 1) & 1);
+      compute(kt & 1);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (all-zero) DMAs must land before smem is reused
   __syncthreads();
 
-  // bias (and the tail layer's BN constants) through the LDS: per-element global loads in the epilogue doubled the time of
+  // bias (and the fused epilogue's constants) through the LDS: per-element global loads in the epilogue doubled the time of
   // memory-bound layers (tools/s1x1_bench.py)
   const float* const sbias = reinterpret_cast<const float*>(smem);
-  const float* const stail = sbias + BN;  // [4][BN]: scale | shift | mean | invstd of the tail layer's channels n0 .. n0 + BN
-  const bool tail = p.tail_y != nullptr;
-  // fused epilogue: out = act((acc + bias) * ep_scale + ep_shift); its constants share the tail layer's LDS rows (never both)
-  constexpr bool ep_on = EPI;  // (the host never combines it with a tail)
-  if (p.bias || tail || ep_on) {
+  const float* const sepi = sbias + BN;  // [2][BN]: ep_scale | ep_shift of the channels n0 .. n0 + BN
+  // fused epilogue: out = act((acc + bias) * ep_scale + ep_shift)
+  constexpr bool ep_on = EPI;
+  if (p.bias || ep_on) {
     if (t < BN) {
       float* const w = reinterpret_cast<float*>(smem);
       if (p.bias) w[t] = (n0 + t < p.bias_n) ? p.bias[n0 + t] : 0.f;
@@ -567,13 +414,6 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
         const int n = n0 + t < p.Nout ? n0 + t : p.Nout - 1;
         w[BN + t] = p.ep_scale ? p.ep_scale[n] : 1.f;
         w[2 * BN + t] = p.ep_scale ? p.ep_shift[n] : 0.f;
-      }
-      if (tail) {
-        const int n = n0 + t < p.Nout ? n0 + t : p.Nout - 1;
-        w[BN + t] = p.tail_scale[n];
-        w[2 * BN + t] = p.tail_shift[n];
-        w[3 * BN + t] = p.tail_mean[n];
-        w[4 * BN + t] = p.tail_invstd[n];
       }
     }
     __syncthreads();
@@ -583,13 +423,6 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   // Nout % 4 == 0 makes every lane's 4-channel group all-valid or all-invalid, so the packed path has no lane-divergent branch
   const bool vec4 = p.y_vec_ok && (p.Nout & 3) == 0;
   const bool rvec = p.res && vec4 && (p.res_ld & 3) == 0 && ((((uintptr_t)p.res) & 7) == 0);
-  const int tact = p.tail_act;
-  const float tap = p.tail_ap;
-  float ts1[NF][4], ts2[NF][4];  // tail: this lane's share of (sum du, sum du * xhat) per channel
-#pragma unroll
-  for (int a = 0; a < NF; ++a)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ts1[a][r] = ts2[a][r] = 0.f;
   // always_inline: an out-of-line instance would take `p` and the accumulators by address — the whole argument block and the
   // accumulator tile then live in scratch memory (measured: 600 B of scratch per lane, the step 30 % slower)
   auto epilogue = [&](auto vec_c) __attribute__((always_inline)) {
@@ -618,7 +451,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
           v3 += bv[3];
         }
         if constexpr (ep_on) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(stail + wn * WN + a * 16 + nq), tv = *reinterpret_cast<const f32x4*>(stail + BN + wn * WN + a * 16 + nq);
+          const f32x4 sv = *reinterpret_cast<const f32x4*>(sepi + wn * WN + a * 16 + nq), tv = *reinterpret_cast<const f32x4*>(sepi + BN + wn * WN + a * 16 + nq);
           float ev[4] = {v0 * sv[0] + tv[0], v1 * sv[1] + tv[1], v2 * sv[2] + tv[2], v3 * sv[3] + tv[3]};
           if (p.res && p.res_pre) {  // residual before the activation (ResNet bottleneck tail)
             const h16_t* rrow = rbase + n;
@@ -655,24 +488,6 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
           u.x = pack2(v0, v1);
           u.y = pack2(v2, v3);
           *reinterpret_cast<uint2*>(yrow + n) = u;
-          if (tail) {  // block-uniform
-            // the sums are taken over the values the tail layer's backward will read: the ROUNDED dz just stored
-            float d[4], yv[4];
-            unpack2(u.x, d[0], d[1]);
-            unpack2(u.y, d[2], d[3]);
-            const uint2 uy = *reinterpret_cast<const uint2*>(p.tail_y + opix * p.tail_y_ld + n);
-            unpack2(uy.x, yv[0], yv[1]);
-            unpack2(uy.y, yv[2], yv[3]);
-            const int cl4 = wn * WN + a * 16 + nq;
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(stail + cl4), sh = *reinterpret_cast<const f32x4*>(stail + BN + cl4);
-            const f32x4 mu = *reinterpret_cast<const f32x4*>(stail + 2 * BN + cl4), is = *reinterpret_cast<const f32x4*>(stail + 3 * BN + cl4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float du = d[r] * act_bwd(yv[r] * sc[r] + sh[r], tact, tap);
-              ts1[a][r] += du;
-              ts2[a][r] += du * ((yv[r] - mu[r]) * is[r]);
-            }
-          }
         } else {
           yrow[n] = (h16_t)v0;
           if (n + 1 < p.Nout) yrow[n + 1] = (h16_t)v1;
@@ -689,9 +504,9 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
   // memory (row pitch BN*2 + 16 bytes: the 16 pixel rows of a fragment land on 16 different 4-bank groups), and after one barrier
   // the tile leaves row by row: one 16-byte store per lane, whole pixel rows contiguous. Same values, same rounding.
   constexpr int EP_PITCH = BN * 2 + 16;
-  constexpr int EP_BASE = 5 * BN * (int)sizeof(float);  // behind the bias / tail constants
+  constexpr int EP_BASE = 5 * BN * (int)sizeof(float);  // behind the bias row and 4 constant rows (2 used: the LDS layout as measured)
   constexpr bool CAN_STAGE = EP_BASE + BM * EP_PITCH <= NST * ST_BYTES;
-  const bool staged = CAN_STAGE && ABL == 0 && !tail && p.staged_epilogue && (p.Nout & 7) == 0 && (p.y_ld & 7) == 0 && ((((uintptr_t)p.y) & 15) == 0);
+  const bool staged = CAN_STAGE && p.staged_epilogue && (p.Nout & 7) == 0 && (p.y_ld & 7) == 0 && ((((uintptr_t)p.y) & 15) == 0);
   if (staged) {
     unsigned char* const tile = smem + EP_BASE;
     // Addend through the LDS (round 6): the skip-connection gradient of dgrad_add was read in the MFMA fragment layout — 8 bytes per
@@ -700,7 +515,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
     // output tile's LDS rows with the store loop's own coalesced pattern (16 bytes per lane, whole pixel rows, every load of a batch
     // independent), and each lane then takes its 4-channel groups from there: same values, same single rounding of acc + addend.
     constexpr int CPR_R = BN / 8;
-    constexpr int RES_IT = BM * CPR_R / (NW * 64);
+    constexpr int RES_IT = BM * CPR_R / 256;
     const bool res_lds = p.staged_epilogue == 2 && p.res && !ep_on && rvec && (p.res_ld & 7) == 0 && ((((uintptr_t)p.res) & 15) == 0);
     if (res_lds) {
       constexpr int RB = BN >= 128 ? (RES_IT < 8 ? RES_IT : 8) : (RES_IT < 4 ? RES_IT : 4);   // loads in flight per lane (the narrow tiles run at a 128-register cap)
@@ -709,7 +524,7 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
         uint4 rv[RB];
 #pragma unroll
         for (int j = 0; j < RB; ++j) {
-          const int idx = t + (it0 + j) * (NW * 64);
+          const int idx = t + (it0 + j) * 256;
           const int row = idx / CPR_R, ch = idx - row * CPR_R;
           const int m = m0 + row;
           rv[j] = uint4{0u, 0u, 0u, 0u};
@@ -724,54 +539,64 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
         }
 #pragma unroll
         for (int j = 0; j < RB; ++j) {
-          const int idx = t + (it0 + j) * (NW * 64);
+          const int idx = t + (it0 + j) * 256;
           const int row = idx / CPR_R, ch = idx - row * CPR_R;
           *reinterpret_cast<uint4*>(tile + row * EP_PITCH + ch * 16) = rv[j];
         }
       }
       __syncthreads();
     }
-    if (consumer) {
 #pragma unroll
-      for (int b = 0; b < MF; ++b) {
-        const int row = wm * WM + b * 16 + (lane & 15);
-        const int m = m0 + row;
-        const h16_t* rbase = nullptr;
-        if (p.res && !res_lds && m < M) {
-          const int n_img = (int)fast_div31((unsigned)m, cl.ohw_mul, cl.ohw_sh);
-          const int rem = m - n_img * OHWi;
-          const int oh = (int)fast_div31((unsigned)rem, cl.ow_mul, cl.ow_sh);
-          const int ow = rem - oh * OWi;
-          const int64_t opix = ((int64_t)n_img * p.OH + (oh * p.out_sh + cl.out_oh)) * p.OW + (ow * p.out_sw + cl.out_ow);
-          rbase = p.res + opix * p.res_ld;
+    for (int b = 0; b < MF; ++b) {
+      const int row = wm * WM + b * 16 + (lane & 15);
+      const int m = m0 + row;
+      const h16_t* rbase = nullptr;
+      if (p.res && !res_lds && m < M) {
+        const int n_img = (int)fast_div31((unsigned)m, cl.ohw_mul, cl.ohw_sh);
+        const int rem = m - n_img * OHWi;
+        const int oh = (int)fast_div31((unsigned)rem, cl.ow_mul, cl.ow_sh);
+        const int ow = rem - oh * OWi;
+        const int64_t opix = ((int64_t)n_img * p.OH + (oh * p.out_sh + cl.out_oh)) * p.OW + (ow * p.out_sw + cl.out_ow);
+        rbase = p.res + opix * p.res_ld;
+      }
+#pragma unroll
+      for (int a = 0; a < NF; ++a) {
+        const int nl = wn * WN + a * 16 + nq;
+        float v0 = acc[a][b][0], v1 = acc[a][b][1], v2 = acc[a][b][2], v3 = acc[a][b][3];
+        if (p.bias) {
+          const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + nl);
+          v0 += bv[0];
+          v1 += bv[1];
+          v2 += bv[2];
+          v3 += bv[3];
         }
+        if constexpr (ep_on) {
+          const f32x4 sv = *reinterpret_cast<const f32x4*>(sepi + nl), tv = *reinterpret_cast<const f32x4*>(sepi + BN + nl);
+          float ev[4] = {v0 * sv[0] + tv[0], v1 * sv[1] + tv[1], v2 * sv[2] + tv[2], v3 * sv[3] + tv[3]};
+          if (rbase && p.res_pre && n0 + nl < p.Nout) {  // (the staged form needs Nout % 8 == 0: the 4 channels exist)
+            const h16_t* rrow = rbase + n0 + nl;
 #pragma unroll
-        for (int a = 0; a < NF; ++a) {
-          const int nl = wn * WN + a * 16 + nq;
-          float v0 = acc[a][b][0], v1 = acc[a][b][1], v2 = acc[a][b][2], v3 = acc[a][b][3];
-          if (p.bias) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + nl);
-            v0 += bv[0];
-            v1 += bv[1];
-            v2 += bv[2];
-            v3 += bv[3];
+            for (int r = 0; r < 4; ++r) ev[r] += (float)rrow[r];
           }
-          if constexpr (ep_on) {
-            const f32x4 sv = *reinterpret_cast<const f32x4*>(stail + nl), tv = *reinterpret_cast<const f32x4*>(stail + BN + nl);
-            float ev[4] = {v0 * sv[0] + tv[0], v1 * sv[1] + tv[1], v2 * sv[2] + tv[2], v3 * sv[3] + tv[3]};
-            if (rbase && p.res_pre && n0 + nl < p.Nout) {  // (the staged form needs Nout % 8 == 0: the 4 channels exist)
-              const h16_t* rrow = rbase + n0 + nl;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) ev[r] += (float)rrow[r];
-            }
-            ig_act_vec<4>(ev, p.ep_act, p.ep_ap);
-            v0 = ev[0];
-            v1 = ev[1];
-            v2 = ev[2];
-            v3 = ev[3];
-          }
-          if (res_lds) {  // (block-uniform) this lane's 4 addend channels from the tile rows filled above; the sum goes back to the same 8 bytes
-            const uint2 u = *reinterpret_cast<const uint2*>(tile + row * EP_PITCH + nl * 2);
+          ig_act_vec<4>(ev, p.ep_act, p.ep_ap);
+          v0 = ev[0];
+          v1 = ev[1];
+          v2 = ev[2];
+          v3 = ev[3];
+        }
+        if (res_lds) {  // (block-uniform) this lane's 4 addend channels from the tile rows filled above; the sum goes back to the same 8 bytes
+          const uint2 u = *reinterpret_cast<const uint2*>(tile + row * EP_PITCH + nl * 2);
+          float r0, r1, r2, r3;
+          unpack2(u.x, r0, r1);
+          unpack2(u.y, r2, r3);
+          v0 += r0;
+          v1 += r1;
+          v2 += r2;
+          v3 += r3;
+        } else if (rbase && !(ep_on && p.res_pre) && n0 + nl < p.Nout) {
+          const h16_t* rrow = rbase + n0 + nl;
+          if (rvec) {
+            const uint2 u = *reinterpret_cast<const uint2*>(rrow);
             float r0, r1, r2, r3;
             unpack2(u.x, r0, r1);
             unpack2(u.y, r2, r3);
@@ -779,34 +604,22 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
             v1 += r1;
             v2 += r2;
             v3 += r3;
-          } else if (rbase && !(ep_on && p.res_pre) && n0 + nl < p.Nout) {
-            const h16_t* rrow = rbase + n0 + nl;
-            if (rvec) {
-              const uint2 u = *reinterpret_cast<const uint2*>(rrow);
-              float r0, r1, r2, r3;
-              unpack2(u.x, r0, r1);
-              unpack2(u.y, r2, r3);
-              v0 += r0;
-              v1 += r1;
-              v2 += r2;
-              v3 += r3;
-            } else {
-              v0 += (float)rrow[0];
-              v1 += (float)rrow[1];
-              v2 += (float)rrow[2];
-              v3 += (float)rrow[3];
-            }
+          } else {
+            v0 += (float)rrow[0];
+            v1 += (float)rrow[1];
+            v2 += (float)rrow[2];
+            v3 += (float)rrow[3];
           }
-          uint2 u;
-          u.x = pack2(v0, v1);
-          u.y = pack2(v2, v3);
-          *reinterpret_cast<uint2*>(tile + row * EP_PITCH + nl * 2) = u;
         }
+        uint2 u;
+        u.x = pack2(v0, v1);
+        u.y = pack2(v2, v3);
+        *reinterpret_cast<uint2*>(tile + row * EP_PITCH + nl * 2) = u;
       }
     }
     __syncthreads();
     constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
-    for (int idx = t; idx < BM * CPR; idx += NW * 64) {
+    for (int idx = t; idx < BM * CPR; idx += 256) {
       const int row = idx / CPR, ch = idx - row * CPR;
       const int m = m0 + row;
       if (m >= M || n0 + ch * 8 >= p.Nout) continue;
@@ -817,40 +630,28 @@ __global__ __launch_bounds__(NW * 64, WS ? 2 : igemm_min_waves(BM, BN, BK, NST, 
       const int64_t opix = ((int64_t)n_img * p.OH + (oh * p.out_sh + cl.out_oh)) * p.OW + (ow * p.out_sw + cl.out_ow);
       *reinterpret_cast<uint4*>(p.y + opix * p.y_ld + n0 + ch * 8) = *reinterpret_cast<const uint4*>(tile + row * EP_PITCH + ch * 16);
     }
-  } else if (ABL == 6) {  // ablation: no output stores (what the epilogue costs); one store keeps the accumulators alive
-    float sacc = 0.f;
-#pragma unroll
-    for (int a = 0; a < NF; ++a)
-#pragma unroll
-      for (int b = 0; b < MF; ++b) sacc += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
-    if (sacc == 123.456f) p.y[0] = (h16_t)sacc;
-  } else if (consumer) {  // (loaders hold no accumulators; they only take part in the barriers below)
-    if (vec4) epilogue(std::true_type{});  // (the host only sets a tail when the packed path applies)
+  } else {
+    if (vec4) epilogue(std::true_type{});
     else epilogue(std::false_type{});
   }
 
   if (p.stats) {
-    if (p.bias || tail || ep_on || staged) __syncthreads();  // the constants / the output tile staged above are dead now
+    if (p.bias || ep_on || staged) __syncthreads();  // the constants / the output tile staged above are dead now
     float* red = reinterpret_cast<float*>(smem);  // [WAVES_M][BN][2]
 #pragma unroll
     for (int a = 0; a < NF; ++a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float s1 = 0.f, s2 = 0.f;
-        if (tail) {
-          s1 = ts1[a][r];
-          s2 = ts2[a][r];
-        } else {
 #pragma unroll
-          for (int b = 0; b < MF; ++b) {
-            const float v = acc[a][b][r];
-            s1 += v;
-            s2 += v * v;
-          }
+        for (int b = 0; b < MF; ++b) {
+          const float v = acc[a][b][r];
+          s1 += v;
+          s2 += v * v;
         }
         s1 = row16_sum(s1);
         s2 = row16_sum(s2);
-        if (consumer && (lane & 15) == 0) {
+        if ((lane & 15) == 0) {
           const int nl = wn * WN + a * 16 + nq + r;
           red[(wm * BN + nl) * 2 + 0] = s1;
           red[(wm * BN + nl) * 2 + 1] = s2;
@@ -946,13 +747,12 @@ static int launch_group(IgemmKernArgs& p, hipStream_t stream) {
   const bool fast = (p.Cin % 32 == 0 || (one_tap && p.Cin % 8 == 0)) && p.Cin <= kFastMaxCin;
   if (p.ep_scale || p.ep_act != CVHIP_ACT_NONE) {
     // fused epilogue: the EPI instances of the same forms
-    if (p.tail_y) return CVHIP_ERR_INVALID;
-    if (fast) hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, 0, NST, 32, true, 4, false, 0, true>), dim3(total), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, 0, NST, 32, false, 4, false, 0, true>), dim3(total), dim3(256), 0, stream, p);
+    if (fast) hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, NST, true, true>), dim3(total), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, NST, false, true>), dim3(total), dim3(256), 0, stream, p);
     return check_launch("igemm_kernel(fused epilogue)");
   }
-  if (fast) hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, 0, NST, 32, true>), dim3(total), dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, 0, NST>), dim3(total), dim3(256), 0, stream, p);
+  if (fast) hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, NST, true>), dim3(total), dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, NST>), dim3(total), dim3(256), 0, stream, p);
   return check_launch("igemm_kernel");
 }
 

@@ -731,7 +731,6 @@ static bool patch_plan(const IgemmParams& p, PatchPlan* pl, bool any_geometry = 
   if (p.ncls < 1 || p.ncls > kKernelClasses) return false;
   if (p.in_sh != p.in_sw || p.in_sh != 1) return false;  // stride-2 inputs: not enabled yet
   if (p.Cin % 32 != 0 || (p.x_ld & 7) != 0) return false;
-  if (p.tail_y) return false;
   const int CK = 32;
   const int BN = p.Nout <= 32 ? 32 : p.Nout <= 64 ? 64 : 128;
   memset(&pl->a, 0, sizeof(pl->a));

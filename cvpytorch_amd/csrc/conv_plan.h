@@ -50,15 +50,6 @@ struct IgemmCommon {
   int il_group, il_tiles, il_order;  // (3) group size, tiles per class, class order packed 4 bits per position
   const h16_t* res;  // optional addend, same pixel grid and channel count as y (dgrad: the gradient arriving over a skip connection)
   int res_ld;
-  // "tail" (dgrad only): this launch produces dz, the gradient at the OUTPUT of a Conv-BN-act layer P (the layer whose activations
-  // were this convolution's input). Its epilogue then also folds P's BatchNorm-backward sums (sum du, sum du * xhat with
-  // du = dz * act'(scale * y + shift), xhat = (y - mean) * invstd) into P's accumulator (`stats` with stats_acc = 1), so that P's
-  // backward needs no reduction pass over (dz, y). tail_y: P's raw convolution output, same pixel grid / channel count as `y` here.
-  const h16_t* tail_y;
-  int tail_y_ld;
-  const float *tail_scale, *tail_shift, *tail_mean, *tail_invstd;
-  int tail_act;
-  float tail_ap;
   // fused EPILOGUE (every conv kernel): out = act((acc + bias) * ep_scale + ep_shift) — a folded / eval-mode BatchNorm and the
   // layer's activation in the convolution's own pass (conv_module.py:201-214 in eval mode, utils/fuse.py:32-54). ep_scale and
   // ep_shift come together or not at all; never combined with `stats` (training-mode sums are those of the raw accumulators).

@@ -113,9 +113,7 @@ __device__ __forceinline__ h16x8 tr_read8(const unsigned char* p0, const unsigne
 // less than the load latency under load: the waves sat in s_waitcnt for 41-59 % of their cycles (profiles/r02_sq_step_summary.txt).
 // Loads are unconditional (masked lanes read the tensor's first bytes and are zeroed on the way into the LDS), so hipcc emits
 // counted vmcnt waits and the younger steps stay in flight across the store of the oldest one.
-// ABL: always 0 in the library (profiling builds of round 2 / 3 used 4 = no fragment reads / MFMAs, 5 = no global
-// loads after the first step (LDS writes, fragment reads and MFMAs only)
-template <int TN, int WN, int WK, int kWgGroups, int PD = 3, int ABL = 0>
+template <int TN, int WN, int WK, int kWgGroups, int PD = 3>
 // (launch bounds: PD 1 with a 128-VGPR cap — 4 blocks per CU instead of 3 — was measured in round 3: the 128-wide tile spills
 // 12-20 B/lane and loses 15-50 % per launch, profiles/r03_wgrad_ablation.log)
 __global__ __launch_bounds__(256 * kWgGroups, kWgGroups == 1 ? 2 : 1) void wgrad_kernel(const WgradParams p) {
@@ -183,7 +181,6 @@ __global__ __launch_bounds__(256 * kWgGroups, kWgGroups == 1 ? 2 : 1) void wgrad
 
   auto load_step = [&](int step, auto setc) {
     constexpr int S = decltype(setc)::value;
-    if (ABL == 5 && step >= PD) return;
     const int mb = m_begin + step * 32;
     unsigned lv = 0;
 #pragma unroll
@@ -217,8 +214,7 @@ __global__ __launch_bounds__(256 * kWgGroups, kWgGroups == 1 ? 2 : 1) void wgrad
     constexpr int S = decltype(setc)::value;
     const uint4 z = make_uint4(0, 0, 0, 0);
     // the oldest step in flight has landed when only the PD-1 younger ones are outstanding (2 + D_IT loads per step, every lane)
-    if (ABL == 5) wgrad_wait_vm<0>();
-    else wgrad_wait_vm<(PD - 1) * (2 + D_IT)>();
+    wgrad_wait_vm<(PD - 1) * (2 + D_IT)>();
 #pragma unroll
     for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(rx[S][i]));
 #pragma unroll
@@ -262,7 +258,6 @@ __global__ __launch_bounds__(256 * kWgGroups, kWgGroups == 1 ? 2 : 1) void wgrad
   const int hsw = q | ((g & 1) << 2);
   const int px0 = 8 * g + q;
   auto compute = [&](int cur) {
-    if (ABL == 4) return;
     h16x8 fd[NF], fx[KF];
 #pragma unroll
     for (int a = 0; a < NF; ++a) {

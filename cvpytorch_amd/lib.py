@@ -41,12 +41,6 @@ class ConvDesc(C.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
-class BnTail(C.Structure):
-    """cvhip_bn_tail (include/cvhip.h)."""
-    _fields_ = [("y", C.c_void_p), ("y_ld", C.c_int32), ("scale", C.c_void_p), ("shift", C.c_void_p), ("mean", C.c_void_p),
-                ("invstd", C.c_void_p), ("act", C.c_int32), ("act_param", C.c_float), ("acc", C.c_void_p), ("acc_ld", C.c_int32)]
-
-
 class ConvFuse(C.Structure):
     """cvhip_conv_fuse (include/cvhip.h): optional fused prologue / epilogue operands of cvhip_conv2d_fprop_fused."""
     _fields_ = [("bias", C.c_void_p), ("stats_partial", C.c_void_p), ("bn_acc", C.c_void_p), ("ep_scale", C.c_void_p),
@@ -161,8 +155,7 @@ SIGNATURES = {
     "cvhip_bn_tail_bwd_sums_acc": (_i32, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i64, _i32, _p, _p, _i32, _f32, _p, _i32, _p]),
     "cvhip_bn_act_bwd_apply_acc": (_i32, [_p, _i32, _p, _i32, _p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _f32, _p]),
     "cvhip_conv1x1_bwd_fused_acc": (_i32, [_dp, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _f32, _p, _i32,
-                                    _p, _i32, _p, _p, _p]),
-    "cvhip_conv2d_dgrad_tail": (_i32, [_dp, _p, _p, _p, _i32, _p, _p, _p]),
+                                    _p, _i32, _p, _p]),
     "cvhip_colsum_partial": (_i32, [_p, _i64, _i32, _i32, _p, _p]),
     "cvhip_colsum_finalize": (_i32, [_p, _i32, _i32, _p, _i32, _p]),
     "cvhip_maxpool2d_fwd": (_i32, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),

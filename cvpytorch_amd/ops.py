@@ -221,13 +221,9 @@ class LazyRaw(torch.Tensor):
 
 
 def tag_lazy(t, lz):
-    """`t` as a LazyRaw carrying the tag (same storage, same autograd node); other engine tags on the tensor object move along"""
+    """`t` as a LazyRaw carrying the tag (same storage, same autograd node)"""
     with torch._C.DisableTorchFunctionSubclass():
         z = t.as_subclass(LazyRaw)
-    for k in ("_hip_prod",):
-        v = getattr(t, k, None)
-        if v is not None:
-            setattr(z, k, v)
     z._hip_lazy = lz
     return z
 
@@ -273,74 +269,6 @@ def materialize(x):
 def _lazy_in(lz):
     """cvhip_lazy_in of a lazy operand (its channel range [lo, hi), constants indexed by the absolute channel)"""
     return L.LazyIn(lz.scale_ptr(), lz.shift_ptr(), lz.act, lz.ap, lz.lo, lz.hi)
-
-
-# ---- producer records: BN-backward sums from the kernel that writes the gradient ------------------------------------------------------
-# The gradient dz at the output of a Conv-BN-act layer P is, for most layers, written by exactly one kernel: the dgrad (or fused
-# 1x1 backward) of the layer that consumed P's output. That kernel can fold P's BatchNorm-backward sums (sum du, sum du*xhat) into
-# P's accumulator in its epilogue (include/cvhip.h cvhip_bn_tail) — P's backward then skips its reduction pass over (dz, y).
-# Plumbing: P's forward hangs a ProdInfo on its output tensor; the consuming op picks it up in its forward, hands the tail to its
-# dgrad in backward and remembers WHICH tensor the sums were taken over; P's backward uses them only if the gradient it receives is
-# that very tensor (autograd summed nothing else into it) — otherwise it clears the accumulator and reduces as before.
-# MEASURED AND LEFT OFF (CVHIP_BN_TAIL, default 0; profiles/r03_bn_tail_ab.log): every form is a net loss on YOLOv5-s — implicit-GEMM
-# dgrad tail +0.2 ms/step, fused 1x1 backward tail +0.28, streaming dgrad tail +0.03 (32 reduction launches deleted, but the epilogues'
-# extra y read in fragment layout and a second SiLU' per element cost more than the 25-30 us reductions they replace).
-_BN_TAIL_MASK = int(__import__("os").environ.get("CVHIP_BN_TAIL", "0"))   # bit 0: implicit-GEMM dgrad, 1: streaming 1x1 dgrad, 2: fused 1x1 backward
-_BN_TAIL = _BN_TAIL_MASK != 0
-_TAIL_ACTS = (L.ACT_NONE, L.ACT_RELU, L.ACT_LEAKY, L.ACT_SILU)
-
-
-class ProdInfo:
-    __slots__ = ("y", "y_ld", "stats", "act", "ap", "acc", "acc_ld", "c_off", "kh", "shape", "consumers", "fused_dx", "done", "parent", "halves")
-
-    def __init__(self, y, y_ld, stats, act, ap, acc, acc_ld, c_off, kh, shape, parent=None):
-        self.y, self.y_ld, self.stats, self.act, self.ap, self.acc, self.acc_ld = y, y_ld, stats, act, ap, acc, acc_ld
-        self.c_off, self.kh, self.shape = c_off, kh, tuple(shape)
-        self.consumers = 0      # Hip conv ops that took the tensor as their input in forward
-        self.fused_dx = None    # the gradient tensor whose rows the sums were taken over (kept alive until P's backward compares)
-        self.done = False
-        self.parent = parent
-        self.halves = None      # sibling pairs: the records of the two output tensors
-
-    def half(self, off, kh):
-        return ProdInfo(self.y, self.y_ld, self.stats, self.act, self.ap, self.acc, self.acc_ld, self.c_off + off, kh,
-                        (self.shape[0], kh, self.shape[2], self.shape[3]), parent=self)
-
-    def tail(self):
-        o4 = 4 * self.c_off
-        st = self.stats
-        return L.BnTail(self.y.data_ptr() + 2 * self.c_off, self.y_ld, st[2].data_ptr() + o4, st[3].data_ptr() + o4, st[0].data_ptr() + o4,
-                        st[1].data_ptr() + o4, self.act, self.ap, self.acc.data_ptr() + 8 * self.c_off, self.acc_ld)
-
-
-def _take_prod(x):
-    """the producer record of an op's input tensor (None unless a training-mode Conv-BN-act layer of this engine made it)"""
-    if not _BN_TAIL or not torch.is_grad_enabled():
-        return None
-    pi = getattr(x, "_hip_prod", None)
-    if pi is not None:
-        pi.consumers += 1
-    return pi
-
-
-def _tail_for(pi, N, Cc, H, W):
-    """cvhip_bn_tail for the dgrad that is about to write dx (N, Cc, H, W dense) of a tensor made by `pi`, or None"""
-    if pi is None or pi.done or pi.consumers != 1 or pi.kh != Cc or pi.shape != (N, Cc, H, W):
-        return None
-    if Cc % 8 or pi.c_off % 8 or pi.y_ld % 8 or (pi.y.data_ptr() + 2 * pi.c_off) % 16:
-        return None
-    return pi.tail()
-
-
-def _sums_already_done(pi, dz):
-    """True when the BN-backward sums of this layer (half) were folded by the kernel that wrote `dz`; if sums were folded for some
-    OTHER tensor (autograd accumulated several gradients) the caller must clear the accumulator and reduce itself -> 'dirty'"""
-    if pi is None or not pi.done:
-        return False
-    fd, pi.fused_dx = pi.fused_dx, None
-    if fd is not None and fd.data_ptr() == dz.data_ptr() and tuple(fd.shape) == tuple(dz.shape) and fd.stride() == dz.stride():
-        return True
-    return "dirty"
 
 
 class KernelTimer:
@@ -395,7 +323,7 @@ def _wgrad_name(k, r=3, s=3, c=0, m=0, desc=None):
     tn = 32 if k <= 32 else 64 if k <= 64 else 128
     if r == 1 and s == 1 and float(m) * k * c <= 7.5e9:
         if k >= 256 and c >= 256:   # launcher policy 4 (conv_wgrad.hip): the 128-wide tile as one two-group block per CU — its own kernel
-            return "wgrad_kernel<128,64,64,2>"   # instance in rocprof (wgrad_kernel<128, 64, 64, 2, 3, 0>), so its own label here
+            return "wgrad_kernel<128,64,64,2>"   # instance in rocprof (wgrad_kernel<128, 64, 64, 2, 3>), so its own label here
         tn = 32
     return {32: "wgrad_kernel<32,32,32>", 64: "wgrad_kernel<64,32,64>", 128: "wgrad_kernel<128,64,64>"}[tn]
 
@@ -542,46 +470,6 @@ def _krsc_master(weight):
     return wk if wk.is_contiguous() else wk.contiguous()
 
 
-# ---- weight-gradient kernels on a side stream -------------------------------------------------------------------------------
-# wgrad of a layer depends only on (x, dy) of that layer and nothing downstream depends on it until the optimizer, while the
-# dgrad -> BN-backward chain is the critical path of backward. Issuing wgrad on a second stream lets it fill the CUs the
-# critical path leaves idle (tile-quantisation tails, low-occupancy small layers). Enabled by arena.FlatTrainState (the
-# gradients land in the arena, nothing on the main stream consumes them before `join_side()`); operands are kept alive until
-# the join so the caching allocator cannot hand their memory to a later main-stream kernel. Under hipGraph capture the
-# fork/join become parallel branches of the graph.
-class _Side:
-    enabled = False
-    after_dgrad = False
-    stream = None
-    keep = []
-    dirty = False
-    # only layers with at most this many output pixel rows go to the side stream (CVHIP_ASYNC_WGRAD_MAXM: the small late layers leave
-    # CUs idle, the large early ones fill the chip by themselves)
-    max_rows = int(__import__("os").environ.get("CVHIP_ASYNC_WGRAD_MAXM", str(1 << 62)))
-
-
-def enable_async_wgrad(flag=True, after_dgrad=False):
-    _Side.enabled = bool(flag)
-    _Side.after_dgrad = bool(after_dgrad)
-
-
-def _side_begin():
-    if _Side.stream is None:
-        _Side.stream = torch.cuda.Stream()
-    _Side.stream.wait_stream(torch.cuda.current_stream())
-    _Side.dirty = True
-    return _Side.stream
-
-
-def join_side():
-    """Make the current stream wait for every side-stream wgrad issued so far and release their operands."""
-    if _Side.dirty:
-        torch.cuda.current_stream().wait_stream(_Side.stream)
-        _Side.dirty = False
-    _Side.keep = []
-
-
-
 class ConvState:
     """Per-layer cache of the bf16 operand images derived from the fp32 master weight."""
 
@@ -684,7 +572,7 @@ class ConvCfg:
     """Static configuration of one conv(+BN+act) layer (python-side)."""
     __slots__ = ("stride", "pad", "dil", "groups", "act", "act_param", "has_bn", "bn_training", "momentum", "eps",
                  "state", "track", "vkey", "gw", "gb", "gg", "gbeta", "arena", "idx_w", "idx_b", "idx_bn", "sync", "out", "out_split", "dx_link", "res_link", "res_pre",
-                 "acc_owner", "acc_attr", "prod", "in_prod", "no_grad", "lazy_out", "lazy_half1", "lazy_half2", "lazy_made", "lazy_made2", "in_lazy", "res_lazy")
+                 "acc_owner", "acc_attr", "no_grad", "lazy_out", "lazy_half1", "lazy_half2", "lazy_made", "lazy_made2", "in_lazy", "res_lazy")
 
     def __init__(self, stride, pad, dil, groups=1, act=L.ACT_NONE, act_param=0.0, has_bn=False, bn_training=True,
                  momentum=0.1, eps=1e-5, state=None, track=True):
@@ -713,9 +601,6 @@ class ConvCfg:
         # module (the BatchNorm layer) that may carry this layer's persistent statistic accumulators, and under which attribute
         self.acc_owner = None
         self.acc_attr = "_hip_acc"
-        # producer records (ProdInfo): `prod` = what this layer's forward made for its output, `in_prod` = its input's record
-        self.prod = None
-        self.in_prod = None
         self.no_grad = False   # conv_bn_act notes whether autograd was recording when the layer was called (inference fast path)
         # lazy activations (LazyAct above): `lazy_out` = the caller wants the RAW output (its consumers transform on load); `lazy_half1`
         # = the same for the first sibling of a pair; `lazy_made` = what forward actually made (None: the activated tensor, as ever);
@@ -864,7 +749,6 @@ def _conv_grads(ctx, x, weight, dy, dy_ld, need_dx, need_dw, need_db):
     elif ctx.has_bias and need_db:
         dbias = zero_fill(torch.empty((K,), dtype=torch.float32, device=dev))  # bias before train-mode BN: zero gradient
     dx = dw = None
-    pending_side = None
     direct_w = arena is not None and cfg.gw is not None and tuple(cfg.gw.shape) == tuple(weight.shape)
     if ctx.depthwise:
         desc = conv_desc(N, Cc, H, W, K, R, S, cfg.stride, cfg.pad, cfg.dil, cfg.groups, x_ld, dy_ld)
@@ -887,20 +771,7 @@ def _conv_grads(ctx, x, weight, dy, dy_ld, need_dx, need_dw, need_db):
             desc = conv_desc(N, Cc, H, W, Kp, R, S, cfg.stride, cfg.pad, cfg.dil, 1, x_ld, dy_ld, kv, cv)
             padded = (Kp != K) or (Cg != Cc)
             geom = (N, Cc, H, W, K, R, S, P, Q)
-            if not padded and direct_w and _Side.enabled and N * P * Q <= _Side.max_rows and not TIMER.enabled and not _DETERMINISTIC and (not arena.multi or arena.defer_allreduce):
-                # same, on the side stream (see _Side): runs concurrently with the BN-backward chain of the layers below. With
-                # _Side.after_dgrad the fork is taken AFTER this layer's dgrad launch, so wgrad (MFMA / LDS bound) shares the chip
-                # with the HBM-bound BN passes that follow instead of with the dgrad kernel (same resources: both slowed down)
-                def side_wgrad(desc=desc):
-                    side = _side_begin()
-                    with torch.cuda.stream(side):
-                        L.call("cvhip_conv2d_wgrad", C.byref(desc), x.data_ptr(), dy.data_ptr(), cfg.gw.data_ptr(), 1, side.cuda_stream)
-                    _Side.keep.append((x, dy))
-                if _Side.after_dgrad and need_dx:
-                    pending_side = side_wgrad
-                else:
-                    side_wgrad()
-            elif not padded and direct_w:
+            if not padded and direct_w:
                 # accumulate straight into the parameter's KRSC slot of the flat gradient arena
                 _wgrad(_wgrad_name(Kp, R, S, Cc, N * P * Q, desc), geom, desc, x, dy, cfg.gw, 1, st)
             elif not padded:
@@ -942,26 +813,6 @@ def _conv_grads(ctx, x, weight, dy, dy_ld, need_dx, need_dw, need_db):
             dx = empty_nhwc(N, Cc, H, W, dev)
             ddesc = conv_desc(N, Cc, H, W, Kp, R, S, cfg.stride, cfg.pad, cfg.dil, 1, Cc, dy_ld, kv, cv)
             link = cfg.dx_link
-            pin = getattr(ctx, "in_prod", None)
-            tail = _tail_for(pin, N, Cc, H, W) if ctx.c_orig == Cc else None
-            if tail is not None:
-                tname = _igemm_name(Cc, N * H * W, -(-R // cfg.stride[0]) * -(-S // cfg.stride[1]) * Kp, _pointwise(R, S, cfg), dy_ld, True)
-                if not (_BN_TAIL_MASK & (2 if tname.startswith("conv1x1_stream") else 1)):
-                    tail = None
-            if tail is not None:
-                # dx is the output gradient of the layer that made x: its BN-backward sums come out of this dgrad's epilogue
-                g, g_ld = None, 0
-                if link is not None and link.g is not None:
-                    g, g_ld = as_nhwc(link.g)
-                    link.g = None
-                    if tuple(g.shape) != (N, Cc, H, W):
-                        raise L.CvhipError("GradLink: skip-connection gradient %s does not match the layer input %s" % (tuple(g.shape), (N, Cc, H, W)))
-                _timed_call(_igemm_name(Cc, N * H * W, -(-R // cfg.stride[0]) * -(-S // cfg.stride[1]) * Kp, _pointwise(R, S, cfg), dy_ld, True), (N, Cc, H, W, K, R, S, P, Q),
-                            "cvhip_conv2d_dgrad_tail", C.byref(ddesc), dy.data_ptr(), ctx.w_dgrad.data_ptr(), _ptr(g), g_ld, dx.data_ptr(), C.byref(tail), st)
-                pin.fused_dx, pin.done = dx, True
-                if pending_side is not None:
-                    pending_side()
-                return dx, dw, dbias
             if link is not None and link.g is not None and ctx.c_orig == Cc:
                 g, g_ld = as_nhwc(link.g)
                 link.g = None
@@ -969,13 +820,9 @@ def _conv_grads(ctx, x, weight, dy, dy_ld, need_dx, need_dw, need_db):
                     raise L.CvhipError("GradLink: skip-connection gradient %s does not match the layer input %s" % (tuple(g.shape), (N, Cc, H, W)))
                 _timed_call(_igemm_name(Cc, N * H * W, -(-R // cfg.stride[0]) * -(-S // cfg.stride[1]) * Kp, _pointwise(R, S, cfg), dy_ld), (N, Cc, H, W, K, R, S, P, Q),
                             "cvhip_conv2d_dgrad_add", C.byref(ddesc), dy.data_ptr(), ctx.w_dgrad.data_ptr(), g.data_ptr(), g_ld, dx.data_ptr(), st)
-                if pending_side is not None:
-                    pending_side()
                 return dx, dw, dbias
             _timed_call(_igemm_name(Cc, N * H * W, -(-R // cfg.stride[0]) * -(-S // cfg.stride[1]) * Kp, _pointwise(R, S, cfg), dy_ld), (N, Cc, H, W, K, R, S, P, Q), "cvhip_conv2d_dgrad", C.byref(ddesc), dy.data_ptr(),
                         ctx.w_dgrad.data_ptr(), dx.data_ptr(), st)
-            if pending_side is not None:
-                pending_side()
     if dw is not None and dw.dtype != weight.dtype:
         dw = dw.to(weight.dtype)
     return dx, dw, dbias
@@ -1099,15 +946,10 @@ def _bwd1x1(ctx, cfg, x, y, weight, segs, k_split, stats, with_mean, ag, ab, act
                     acc.data_ptr(), K, _ptr(g_out), _ptr(b_out), int(accumulate), act, act_param, _ptr(g), g_ld,
                     dx.data_ptr(), Cc, dst.data_ptr(), C.byref(li), st, passes=2, nbytes=2.0 * M * (2 * K + 2 * Cc))
     elif acc is not None:
-        pin = getattr(ctx, "in_prod", None)
-        tail = _tail_for(pin, N, Cc, H, W) if (_BN_TAIL_MASK & 4) else None
         _timed_call("bwd1x1_kernel", (N, Cc, H, W, K, R, S, P, Q), "cvhip_conv1x1_bwd_fused_acc", C.byref(desc), d0.data_ptr(), d0_ld,
                     _ptr(d1), d1_ld, k_split, y.data_ptr(), x.data_ptr(), ctx.w_dgrad.data_ptr(), sc, sh, mu, isd,
                     acc.data_ptr(), K, _ptr(g_out), _ptr(b_out), int(accumulate), act, act_param, _ptr(g), g_ld,
-                    dx.data_ptr(), Cc, dst.data_ptr(), C.byref(tail) if tail is not None else None, st, passes=2,
-                    nbytes=2.0 * M * (2 * K + 2 * Cc + (Cc if tail is not None else 0)))
-        if tail is not None:
-            pin.fused_dx, pin.done = dx, True
+                    dx.data_ptr(), Cc, dst.data_ptr(), st, passes=2, nbytes=2.0 * M * (2 * K + 2 * Cc))
     else:
         _timed_call("bwd1x1_kernel", (N, Cc, H, W, K, R, S, P, Q), "cvhip_conv1x1_bwd_fused", C.byref(desc), d0.data_ptr(), d0_ld,
                     _ptr(d1), d1_ld, k_split, y.data_ptr(), x.data_ptr(), ctx.w_dgrad.data_ptr(), sc, sh, mu, isd,
@@ -1208,7 +1050,6 @@ def _conv_fused_inference(x, x_ld, weight, bias, gamma, beta, running_mean, runn
         f.residual_pre = int(bool(cfg.res_pre))   # ResNet bottleneck tail: relu(bn3(conv3) + identity)
     kname = "conv_fused_inference"
     _timed_call(kname, geom, "cvhip_conv2d_fprop_fused", C.byref(desc), x.data_ptr(), cfg.state.w_fprop.data_ptr(), z.data_ptr(), C.byref(f), st)
-    cfg.prod = None
     return z
 
 
@@ -1292,7 +1133,6 @@ class ConvBnAct(torch.autograd.Function):
                 zdesc = conv_desc(N, Cc, H, W, K, R, S, cfg.stride, cfg.pad, cfg.dil, cfg.groups, x_ld, z_ld)
                 _timed_ew("dw_fused_inference", 2.0 * (N * H * W * Cc + M * K), "cvhip_dwconv2d_fprop_act", C.byref(zdesc), x.data_ptr(), wf.data_ptr(),
                           _ptr(bf), int(cfg.act), float(cfg.act_param), z.data_ptr(), st)
-                cfg.prod = None
                 return z
             dw_rows = 0
             if train_bn and _DW_STATS and Kp == K:
@@ -1464,15 +1304,10 @@ class ConvBnAct(torch.autograd.Function):
         ctx.has_res = residual is not None
         ctx.w_dgrad = cfg.state.w_dgrad if not depthwise else None
         ctx.acc_b = acc_b if use_acc else None   # this application's backward accumulator (sum du, sum du*xhat), zeroed
-        ctx.in_prod = cfg.in_prod if (need_dx and not depthwise and c_orig == Cc) else None
         ctx.in_lazy = cfg.in_lazy   # x (saved below) is then the producer's RAW output: backward transforms it on load too
-        cfg.prod = ctx.prod = None
-        if use_acc and _BN_TAIL and cfg.act in _TAIL_ACTS and not (cfg.res_pre and residual is not None) and any(ctx.needs_input_grad):  # (grad mode is off inside forward)
-            cfg.prod = ctx.prod = ProdInfo(y, Kp, stats, cfg.act, cfg.act_param, acc_b, K, 0, K, (N, K, P, Q))
         ctx.res_pre = bool(cfg.res_pre and residual is not None and not isinstance(z, tuple))
         ctx.split2 = split2 is not None
         if split2 is not None:
-            cfg.prod = ctx.prod = None
             ctx.save_for_backward(x, y, stats, weight, z[1])   # y's channels [k1, K) were never written: the raw half lives in the concat slice
         elif ctx.res_pre:
             ctx.save_for_backward(x if image is None else image, y, stats, weight, z)   # the activation's derivative is taken from the OUTPUT's sign
@@ -1527,18 +1362,12 @@ class ConvBnAct(torch.autograd.Function):
             lzi = None
         direct_bn = arena is not None and cfg.gg is not None and cfg.gbeta is not None
         if acc_b is not None:
-            # (sum du, sum du*xhat) into the layer's accumulator — unless the kernel that wrote dz already folded them in
-            # (ProdInfo); the consumer below folds the accumulator and stores dgamma / dbeta
+            # (sum du, sum du*xhat) into the layer's accumulator — unless the residual-tail pass above already reduced while it
+            # masked; the consumer below folds the accumulator and stores dgamma / dbeta
             if getattr(ctx, "_acc_b_used", False):
                 zero_fill(acc_b)   # backward(retain_graph=True) a second time: the sums of the first pass must not be added twice
             ctx._acc_b_used = True
-            have = _sums_already_done(getattr(ctx, "prod", None), dz)
-            if have == "dirty":
-                zero_fill(acc_b)
-                have = False
-            if tail_sums_done:
-                have = True   # (the residual-tail pass above reduced while it masked)
-            if not have:
+            if not tail_sums_done:
                 _timed_ew("bn_act_bwd_sums(colreduce_kernel<1>)", 4.0 * M * K, "cvhip_bn_act_bwd_sums_acc", dz.data_ptr(), dz_ld, y.data_ptr(), Kp, M, K,
                           stats[2].data_ptr(), stats[3].data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), act, act_param, acc_b.data_ptr(), K, st)
             if direct_bn:
@@ -1708,12 +1537,9 @@ def _admit_lazy(x, residual, K, R, S, has_bias, cfg):
 
 
 def conv_bn_act(x, weight, bias, gamma, beta, running_mean, running_var, residual, cfg):
-    cfg.in_prod = _take_prod(x)
     cfg.no_grad = not torch.is_grad_enabled()   # (inside Function.forward grad mode is always off: note it here)
     x, residual = _admit_lazy(x, residual, weight.shape[0], weight.shape[2], weight.shape[3], bias is not None, cfg)
     z = ConvBnAct.apply(x, weight, bias, gamma, beta, running_mean, running_var, residual, cfg)
-    if cfg.prod is not None and torch.is_tensor(z):
-        z._hip_prod = cfg.prod
     if cfg.lazy_made is not None and torch.is_tensor(z):
         st4, off, kh = cfg.lazy_made
         z = tag_lazy(z, LazyAct(st4[2][off:off + kh], st4[3][off:off + kh], cfg.act, cfg.act_param))
@@ -1760,15 +1586,7 @@ class ConvBnActPair(torch.autograd.Function):
         if acc_b is not None:
             # per-half sums into the pair's accumulator, then either ONE fused kernel or per-half apply passes that fold it themselves
             halves = list(zip(segs, (ctx.k1, K - ctx.k1), (0, ctx.k1)))
-            pi = getattr(ctx, "prod", None)
-            have = [(_sums_already_done(h, d) if pi is not None and pi.halves is not None else False)
-                    for h, ((d, _), _, _) in zip(pi.halves if (pi is not None and pi.halves is not None) else (None, None), halves)]
-            if "dirty" in have:   # sums were folded over a tensor that is not the gradient we received: start over
-                zero_fill(acc_b)
-                have = [False, False]
-            for ((d, d_ld), kh, off), hv, (ya, ya_ld) in zip(halves, have, yat):
-                if hv:
-                    continue
+            for ((d, d_ld), kh, off), (ya, ya_ld) in zip(halves, yat):
                 sc, sh, mean, invstd = (stats[i].data_ptr() + 4 * off for i in (2, 3, 0, 1))
                 _timed_ew("bn_act_bwd_sums(colreduce_kernel<1>)", 4.0 * M * kh, "cvhip_bn_act_bwd_sums_acc", d.data_ptr(), d_ld, ya, ya_ld, M, kh,
                           sc, sh, mean, invstd, cfg.act, cfg.act_param, acc_b.data_ptr() + 8 * off, K, st)
@@ -1874,7 +1692,6 @@ def conv_bn_act_pair(x, operands, cfg, out2=None):
     wf, gf, bf, rmf, rvf, gw, gg, gb, arena, idx_w, idx_bn, k1 = operands
     cfg.out_split = (k1, out2) if out2 is not None else None
     cfg.arena, cfg.gw, cfg.gg, cfg.gbeta, cfg.idx_w, cfg.idx_bn = arena, gw, gg, gb, idx_w, idx_bn
-    cfg.in_prod = _take_prod(x)
     x, _ = _admit_lazy(x, None, wf.shape[0], 1, 1, False, cfg)
     z1, z2 = ConvBnActPair.apply(x, wf, gf, bf, rmf, rvf, cfg, k1)
     if cfg.lazy_made is not None:   # the first sibling's result is lazy: z1 is the channel slice [0, k1) of the pair's raw output
@@ -1883,10 +1700,6 @@ def conv_bn_act_pair(x, operands, cfg, out2=None):
     if cfg.lazy_made2 is not None:  # the second sibling's slice of the concat buffer holds its RAW output (split store)
         st4, off, kh = cfg.lazy_made2
         z2 = tag_lazy(z2, LazyAct(st4[2][off:off + kh], st4[3][off:off + kh], cfg.act, cfg.act_param))
-    if cfg.prod is not None:
-        kt = cfg.prod.kh
-        cfg.prod.halves = (cfg.prod.half(0, k1), cfg.prod.half(k1, kt - k1))
-        z1._hip_prod, z2._hip_prod = cfg.prod.halves
     return z1, z2
 
 

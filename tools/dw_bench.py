@@ -1,11 +1,12 @@
-"""Dev tool: depthwise 3x3 fprop / dgrad / wgrad on the DeepLabv3+ decoder shapes (env CVHIP_DW3_SEG / CVHIP_DW3_RPT sweep the walk geometry)."""
+"""Dev tool: depthwise 3x3 fprop / dgrad / wgrad on the DeepLabv3+ decoder shapes (CVHIP_DW3_LDS=0: the register-window kernels
+instead of the LDS strip kernels)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cvpytorch_amd import ops, lib as L
 dev = torch.device("cuda:0")
 BF = torch.bfloat16
-tag = "seg=%s rpt=%s" % (os.environ.get("CVHIP_DW3_SEG", "-"), os.environ.get("CVHIP_DW3_RPT", "-"))
+tag = "lds=%s" % os.environ.get("CVHIP_DW3_LDS", "-")
 for (N, Cc, H, W) in [(16, 304, 128, 256), (16, 256, 128, 256)]:
     x = torch.randn(N, H, W, Cc, device=dev).to(BF)
     y = torch.empty_like(x)

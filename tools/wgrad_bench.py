@@ -1,5 +1,6 @@
-"""Dev tool: time cvhip_conv2d_wgrad on the YOLOv5-s / DeepLabv3+ layer shapes (batch 64 / 16), e.g. under CVHIP_WGRAD_ABLATE=1/4/5
-(no atomic epilogue / staging only / no global loads) to split a launch into its parts."""
+"""Dev tool: time cvhip_conv2d_wgrad on the YOLOv5-s / DeepLabv3+ layer shapes (batch 64 / 16), e.g. under CVHIP_WGRAD_BAND=0/1/2
+(general kernel everywhere / default policy / tap-resident kernel wherever the geometry allows); the CVHIP_* settings of the run
+label its output line."""
 import ctypes as C
 import os
 import sys
@@ -20,7 +21,7 @@ if os.environ.get("WG_ONLY") == "k1":
     SHAPES = [sh for sh in SHAPES if sh[5] == 1]
 elif os.environ.get("WG_ONLY") == "k3":
     SHAPES = [sh for sh in SHAPES if sh[5] == 3]
-tag = " ".join("%s=%s" % (k[6:], v) for k, v in sorted(os.environ.items()) if k.startswith("CVHIP_WGRAD"))
+tag = " ".join("%s=%s" % (k[6:], v) for k, v in sorted(os.environ.items()) if k.startswith("CVHIP_"))
 st = torch.cuda.current_stream().cuda_stream
 tot = 0.0
 for (N, Cc, H, W, K, R, s) in SHAPES:
