@@ -1,6 +1,10 @@
 """bench.py — images/sec of one full YOLOv5-s train step (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+`--full` adds everything else the line can carry (the objects below, and at N > 1 the gradient-exchange and SyncBN legs); the
+--no-* switches of those legs apply under --full.
 
 N > 1: either torch.distributed.run starts the N ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment: the driver's
 form, reference README.md:127 `python -m torch.distributed.launch --nproc_per_node=N trainer.py`), or — when WORLD_SIZE is not
@@ -13,9 +17,11 @@ loss -> backward (+ bucketed RCCL gradient all-reduce) -> SGD(nesterov) -> zero_
 synthetic COCO-shape batch already resident in HBM (640x640, bf16 activations,
 per-GPU batch 64, weak scaling). One JSON line on rank 0.
 
-Extra objects:
+Extra objects (--full):
   roofline     : the dominant kernel of the step (by summed launch time; HIP events on the launch stream around EVERY conv,
-                 fused-backward and BN/activation launch) against the MI355X roofline that binds it (MI355X_MICROARCH.md:
+                 fused-backward and BN/activation launch of an eager re-run of the K steps after the timed region; when the timed
+                 steps themselves run eagerly, e.g. --no-graph, the events ride inside them and this object needs no --full)
+                 against the MI355X roofline that binds it (MI355X_MICROARCH.md:
                  2.5 PFLOP/s dense bf16 MFMA, 8 TB/s HBM3E), `conv_roofline` the same for the dominant MFMA conv kernel.
                  Algorithmic flops/bytes per launch: DESIGN.md §4. `peaks_measured`: what a plain device copy and a bare
                  MFMA loop reach on THIS box (the attainable ceilings beside the nominal ones).
@@ -53,6 +59,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (conf/coco_yolov5_s.yml:17)")
     ap.add_argument("--size", type=int, default=640)
+    ap.add_argument("--full", action="store_true", help="after the headline, also run everything else the line can carry: the per-kernel "
+                    "re-run and roofline objects, measured peaks, the host-fed leg, the inference legs, the side workloads (other models, "
+                    "sizes and precisions), the CPU baseline, and at N > 1 the gradient-exchange and SyncBN legs. A plain run does none of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
@@ -814,7 +823,7 @@ def main():
     if a.dump_outputs and rank == 0:   # before the eager re-run below, which trains the same model further
         dump_outputs(a.dump_outputs, model, losses)
     timing_source = "HIP events around every conv launch inside the timed region (eager)"
-    if use_graph and not a.no_kernel_timing:  # every rank takes part (the steps contain collectives); only rank 0 records events
+    if a.full and use_graph and not a.no_kernel_timing:  # every rank takes part (the steps contain collectives); only rank 0 records events
         # per-kernel events cannot ride inside a graph replay: time the same K steps once more, eagerly, right after
         step.graph = None
         ops.TIMER.enabled = rank == 0
@@ -880,7 +889,7 @@ def main():
             out["step_roofline"] = {"mfma_frac": round(ips_gpu * 49.30e9 / (PEAK_MFMA_TFLOPS * 1e12), 4),
                                     "hbm_frac": round(ips_gpu * 366e6 / (PEAK_HBM_GBS * 1e9), 4)}
 
-    # ---- side legs: everything below is extra keys of the same line; a leg that fails or hangs must not cost the headline ----
+    # ---- side legs (--full; config.ranks at N > 1 always): extra keys of the same line; a leg that fails or hangs must not cost the headline ----
     dog = _Watchdog(out, rank, float(os.environ.get("CVHIP_BENCH_SIDE_BUDGET", "900")))
     if world > 1:
         # what every rank saw: its HIP device and the world size its communicator reports (the record shows RCCL ran N ranks)
@@ -893,7 +902,7 @@ def main():
         except Exception as e:
             if rank == 0:
                 out["config"]["ranks"] = {"error": repr(e)[:200]}
-    if world > 1 and not a.no_exchange_ab and not a.stock_optimizer and not a.sync_bn:
+    if a.full and world > 1 and not a.no_exchange_ab and not a.stock_optimizer and not a.sync_bn:
         # ONE invocation answers the open questions of the gradient exchange: ring all-reduce per bucket vs
         # reduce-scatter + all-gather of the same range, and 8 vs 25 MiB buckets — the same K steps for each, same synthetic batch
         res = {}
@@ -921,7 +930,7 @@ def main():
             res["allreduce_8mib"] = {"value": out["value"], "ms_per_step": out["ms_per_step"], "ms_per_step_median": out["ms_per_step_median"],
                                      "grad_buckets": out["config"]["grad_buckets"], "what": "the headline configuration"}
             out["grad_exchange_ab"] = res
-    if world > 1 and not a.no_sync_bn_leg and not a.sync_bn and not a.stock_optimizer:
+    if a.full and world > 1 and not a.no_sync_bn_leg and not a.sync_bn and not a.stock_optimizer:
         # the reference forces SyncBN under DDP (trainer.py:126-127); SURVEY.md §8(d) config 4: report both
         try:
             step = None
@@ -942,7 +951,7 @@ def main():
         except Exception as e:
             if rank == 0:
                 out["with_sync_bn"] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         if not a.no_kernel_timing:
             try:
                 out["peaks_measured"] = measured_peaks(dev)

@@ -42,16 +42,19 @@ def test_dump_outputs_refuses_more_than_64_mb(tmp_path):
 def test_bench_dumps_the_last_timed_step_the_same_every_run(tmp_path):
     runs = []
     for i, timing in enumerate((False, True)):
-        # the second run also times every kernel in an eager re-run of the K steps after the timed region: the dump must be taken
-        # before it (the re-run trains the same model further), so both runs write the same arrays
+        # the first run is a plain one (headline only); the second, under --full, also times every kernel in an eager re-run of the
+        # K steps after the timed region: the dump must be taken before it (the re-run trains the same model further), so both runs
+        # write the same arrays
         out = tmp_path / ("dump%d" % i)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--size", "256",
-               "--no-cpu-baseline", "--no-deeplab", "--no-h2d", "--no-extra", "--dump-outputs", str(out)] + ([] if timing else ["--no-kernel-timing"])
+               "--dump-outputs", str(out)] + (["--full", "--no-cpu-baseline", "--no-deeplab", "--no-h2d", "--no-extra"] if timing else [])
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
         assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["deterministic"] is True
-        assert ("kernels" in line) == timing
+        assert ("kernels" in line) == timing and ("peaks_measured" in line) == timing
+        if not timing:   # a plain run carries the headline alone
+            assert not set(line) & {"roofline", "with_h2d", "infer", "config3_deeplabv3plus_r50", "config4_yolox_s", "cpu_baseline"}, sorted(line)
         files = {f[:-4]: str(out / f) for f in os.listdir(str(out))}
         assert set(files) == {"loss", "box_loss", "obj_loss", "cls_loss", "parameters", "buffers"}
         assert sum(os.path.getsize(f) for f in files.values()) <= 64 << 20

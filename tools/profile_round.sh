@@ -11,10 +11,10 @@ mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 stats_csv() { find $1 -name "*kernel_stats.csv" | head -1; }
 if has bench; then
-  timeout 900 python $R/bench.py 2>$O/${TAG}_bench_final.err | tail -1 > $O/${TAG}_bench_final.json.log
+  timeout 900 python $R/bench.py --full 2>$O/${TAG}_bench_final.err | tail -1 > $O/${TAG}_bench_final.json.log
 fi
 if has stats; then
-  rm -rf /tmp/p_def; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_def -- python $R/bench.py 2>/dev/null | tail -1 > $O/${TAG}_default_bench_under_rocprof.json.log
+  rm -rf /tmp/p_def; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_def -- python $R/bench.py --full 2>/dev/null | tail -1 > $O/${TAG}_default_bench_under_rocprof.json.log
   cp $(stats_csv /tmp/p_def) $O/${TAG}_default_bench_kernel_stats.csv
 fi
 if has y5s; then
