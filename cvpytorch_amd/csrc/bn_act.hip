@@ -42,11 +42,14 @@ struct RedParams {
   float* partial;  // [gridDim.x][2][C]
   double* acc;     // or: fp64 accumulator [kAccShards][2][acc_ld] (atomics; common.h acc_add2) — no partial rows, no finalize launch
   int acc_ld;
+  int addr32;      // a block's rows times the pitch fit 31 bits for every operand: 32-bit lane offsets (set by red_launch_dims)
 };
 
 // ACT: compile-time activation id for MODE 1 (a runtime switch inside the element loop compiles to a chain of scalar
 // branches per element)
-template <int MODE, int ACT = 0>
+// A32: the lanes address the operands with 32-bit byte offsets from block-uniform bases (RedParams::addr32 holds); a kernel of its own
+// rather than a branch, so that each form is register-allocated alone
+template <int MODE, int ACT = 0, bool A32 = true>
 __global__ __launch_bounds__(256) void colreduce_kernel(const RedParams p) {
   __shared__ float red[256 * 16];
   const int t = threadIdx.x;
@@ -65,9 +68,9 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const RedParams p) {
 
   for (int cv0 = 0; cv0 < CV; cv0 += cols_per_pass) {
     const int cv = cv0 + tx;
-    float s1[8], s2[8];
+    f32x2 s1[4], s2[4];  // 8 channels as 4 pairs (common.h, pair-wise forms)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
+    for (int k = 0; k < 4; ++k) s1[k] = s2[k] = f32x2{0.f, 0.f};
     float sc[8], sh[8], mu[8], is[8];
     fill8c(1.f, sc);
     fill8c(0.f, sh);
@@ -85,48 +88,76 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const RedParams p) {
       }
     }
     if (active && cv < CV) {
+      // element-wise form: MODE 0 / 2, and every mode on the scalar path
       auto accum = [&](const f32x8& a, const f32x8& y) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
+          float t1 = s1[j >> 1][j & 1], t2 = s2[j >> 1][j & 1];
           if (MODE == 0) {
-            s1[j] += a.v[j];
-            s2[j] += a.v[j] * a.v[j];
+            t1 += a.v[j];
+            t2 += a.v[j] * a.v[j];
           } else if (MODE == 2) {
-            s1[j] += a.v[j];
+            t1 += a.v[j];
           } else if (MODE == 3) {
             // a = du (already masked and rounded to 16 bits by the caller below): the BatchNorm branch has no activation of its own
             const float xh = (y.v[j] - mu[j]) * is[j];
-            s1[j] += a.v[j];
-            s2[j] += a.v[j] * xh;
+            t1 += a.v[j];
+            t2 += a.v[j] * xh;
           } else {
             const float u = y.v[j] * sc[j] + sh[j];
             const float du = a.v[j] * act_bwd(u, ACT, p.ap);
             const float xh = (y.v[j] - mu[j]) * is[j];
-            s1[j] += du;
-            s2[j] += du * xh;
+            t1 += du;
+            t2 += du * xh;
           }
+          s1[j >> 1][j & 1] = t1;
+          s2[j >> 1][j & 1] = t2;
         }
       };
-      int64_t r = r_begin + ty;
-      if (vec) {
-        // 4 rows per trip: 4-8 independent 16-B loads in flight per lane before any arithmetic (HBM latency hiding). The LAST trip
-        // of a block is the same code with its missing rows masked (clamped address, zero contribution): a remainder walked one
-        // row per iteration cost up to 3 extra dependent memory round trips per block — on the 26 MB layers (100 rows per block,
-        // one 64-row trip + 36 rows of remainder) more than the trip itself (2.4 TB/s against 3.8 for the aligned shapes).
-        // (Software-pipelining the trips — next trip's loads issued before this trip's arithmetic — was measured in round 3: +32
-        // VGPRs, no gain on the backward passes: they are co-limited by the quarter-rate v_exp_f32 / v_rcp_f32 of the SiLU derivative.)
-        const int64_t stp = rows_per_pass;
-        for (; r < r_end; r += 4 * stp) {
+      // 4 rows per trip: 4-8 independent 16-B loads in flight per lane before any arithmetic (HBM latency hiding). The LAST trip
+      // of a block is the same code with its missing rows masked (clamped address, zero contribution): a remainder walked one
+      // row per iteration cost up to 3 extra dependent memory round trips per block — on the 26 MB layers (100 rows per block,
+      // one 64-row trip + 36 rows of remainder) more than the trip itself (2.4 TB/s against 3.8 for the aligned shapes).
+      // (Software-pipelining the trips — next trip's loads issued before this trip's arithmetic — was measured in round 3: +32
+      // VGPRs, no gain on the backward passes: they are co-limited by the quarter-rate v_exp_f32 / v_rcp_f32 of the SiLU derivative.)
+      //
+      // Addresses: the operand bases are block-uniform (advanced to the block's first row), a lane keeps one byte offset per operand
+      // relative to them and adds a loop-invariant stride per trip. OFF is uint32_t when the host found that a block's rows times the
+      // pitch fit 31 bits for every operand (RedParams::addr32; the loads then take the scalar-base + 32-bit-offset form and no trip
+      // does 64-bit multiplies or adds in the VALU), int64_t otherwise.
+      auto trips = [&]() {
+        using OFF = std::conditional_t<A32, uint32_t, int64_t>;
+        const int64_t left = r_end - r_begin;
+        const OFF nr = (OFF)(left > 0 ? left : 0);
+        const OFF stp = (OFF)rows_per_pass;
+        const char* ab = reinterpret_cast<const char*>(p.a + r_begin * p.ld_a);
+        const char* yb = reinterpret_cast<const char*>(p.y + ((MODE == 1 || MODE == 3) ? r_begin * p.ld_y : 0));
+        const char* zb = reinterpret_cast<const char*>(p.z + (MODE == 3 ? r_begin * p.ld_z : 0));
+        char* db = reinterpret_cast<char*>(p.du + (MODE == 3 ? r_begin * p.ld_du : 0));
+        const OFF da = stp * (OFF)p.ld_a * 2, dy = stp * (OFF)p.ld_y * 2, dzs = stp * (OFF)p.ld_z * 2, dd = stp * (OFF)p.ld_du * 2;
+        OFF oa = ((OFF)ty * (OFF)p.ld_a + (OFF)cv * 8) * 2, oy = ((OFF)ty * (OFF)p.ld_y + (OFF)cv * 8) * 2;
+        OFF oz = ((OFF)ty * (OFF)p.ld_z + (OFF)cv * 8) * 2, od = ((OFF)ty * (OFF)p.ld_du + (OFF)cv * 8) * 2;
+        f32x2 sc2[4], sh2[4], mu2[4], is2[4];
+        pairs_of(sc, sc2);
+        pairs_of(sh, sh2);
+        pairs_of(mu, mu2);
+        pairs_of(is, is2);
+        for (OFF rr = (OFF)ty; rr < nr; rr += 4 * stp) {
           uint4 ua[4], uy[4], uz[MODE == 3 ? 4 : 1];
           bool ok[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int64_t rq = r + q * stp;
-            ok[q] = rq < r_end;
-            const int64_t rc = ok[q] ? rq : r;
-            ua[q] = *reinterpret_cast<const uint4*>(p.a + rc * p.ld_a + cv * 8);
-            if (MODE == 1 || MODE == 3) uy[q] = *reinterpret_cast<const uint4*>(p.y + rc * p.ld_y + cv * 8);
-            if constexpr (MODE == 3) uz[q] = *reinterpret_cast<const uint4*>(p.z + rc * p.ld_z + cv * 8);
+            ok[q] = rr + (OFF)q * stp < nr;
+            if constexpr (A32) {
+              ua[q] = *reinterpret_cast<const uint4*>(ab + (ok[q] ? oa + (OFF)q * da : oa));
+              if (MODE == 1 || MODE == 3) uy[q] = *reinterpret_cast<const uint4*>(yb + (ok[q] ? oy + (OFF)q * dy : oy));
+              if constexpr (MODE == 3) uz[q] = *reinterpret_cast<const uint4*>(zb + (ok[q] ? oz + (OFF)q * dzs : oz));
+            } else {  // 64-bit: the row's address from its index, every trip
+              const int64_t rc = r_begin + (ok[q] ? rr + (OFF)q * stp : rr);
+              ua[q] = *reinterpret_cast<const uint4*>(p.a + rc * p.ld_a + cv * 8);
+              if (MODE == 1 || MODE == 3) uy[q] = *reinterpret_cast<const uint4*>(p.y + rc * p.ld_y + cv * 8);
+              if constexpr (MODE == 3) uz[q] = *reinterpret_cast<const uint4*>(p.z + rc * p.ld_z + cv * 8);
+            }
           }
           // every load of the trip is issued before any arithmetic: without the fence hipcc's scheduler sinks the loads of rows
           // 1..3 below the arithmetic of row 0 (fewer live registers) and waits vmcnt(0) after each — one row in flight per lane
@@ -137,46 +168,76 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const RedParams p) {
             // the SiLU derivative is ~40 VALU instructions per element, and with 1024 blocks the mid-size layers run 1.56 / 3.125
             // trips per lane, i.e. up to 22 % masked slots — is skipped under a wave-uniform branch. Adding +0 changed no sum before.
             if (__builtin_amdgcn_ballot_w64(ok[q]) == 0) continue;
-            if (!ok[q]) ua[q] = make_uint4(0u, 0u, 0u, 0u);  // x = 0 / dz = 0: no contribution to either sum
+            if (!ok[q]) ua[q] = make_uint4(0u, 0u, 0u, 0u);  // x = 0 / dz = 0: no contribution to either sum (one select on the packed words)
             if constexpr (MODE == 3) {
               // du = dz * act'(z), rounded to 16 bits (what the stand-alone apply pass stores and the reduction pass then reads)
-              f32x8 d = unpack8(ua[q]);
-              const f32x8 zz = unpack8(uz[q]);
+              f32x2 d[4], zz[4], yy[4];
+              unpack_pairs(ua[q], d);
+              unpack_pairs(uz[q], zz);
+              unpack_pairs(uy[q], yy);
 #pragma unroll
-              for (int j = 0; j < 8; ++j) d.v[j] *= act_bwd(zz.v[j], ACT, p.ap);
-              const uint4 packed = pack8(d);
-              if (ok[q]) *reinterpret_cast<uint4*>(p.du + (r + q * stp) * p.ld_du + cv * 8) = packed;
-              accum(unpack8(packed), unpack8(uy[q]));
+              for (int k = 0; k < 4; ++k) d[k] = d[k] * act_bwd2<ACT>(zz[k], p.ap);
+              const uint4 packed = pack_pairs(d);
+              if (ok[q]) {
+                if constexpr (A32) *reinterpret_cast<uint4*>(db + (od + (OFF)q * dd)) = packed;
+                else *reinterpret_cast<uint4*>(p.du + (r_begin + rr + (OFF)q * stp) * p.ld_du + cv * 8) = packed;
+              }
+              unpack_pairs(packed, d);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) bn_bwd_sums2(d[k], yy[k], mu2[k], is2[k], s1[k], s2[k]);
+            } else if constexpr (MODE == 1) {
+              f32x2 d[4], yy[4];
+              unpack_pairs(ua[q], d);
+              unpack_pairs(uy[q], yy);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                // the first row of a trip has always added the rounded du of the sigmoid-based activations to s1 and rows 1..3 the
+                // fused product (what the optimizer made of the element-wise source); kept, so that the sums stay bit-identical
+                if (q == 0 && (ACT == CVHIP_ACT_SILU || ACT == CVHIP_ACT_SIGMOID)) bnact_bwd_sums2<ACT, false>(d[k], yy[k], sc2[k], sh2[k], mu2[k], is2[k], p.ap, s1[k], s2[k]);
+                else bnact_bwd_sums2<ACT, true>(d[k], yy[k], sc2[k], sh2[k], mu2[k], is2[k], p.ap, s1[k], s2[k]);
+              }
             } else {
-              accum(unpack8(ua[q]), MODE == 1 ? unpack8(uy[q]) : f32x8{});
+              accum(unpack8(ua[q]), f32x8{});
+            }
+          }
+          if constexpr (A32) {
+            oa += 4 * da;
+            if (MODE == 1 || MODE == 3) oy += 4 * dy;
+            if constexpr (MODE == 3) {
+              oz += 4 * dzs;
+              od += 4 * dd;
             }
           }
         }
-      }
-      for (; r < r_end; r += rows_per_pass) {  // (scalar path only: the vector loop above leaves nothing)
-        f32x8 a, y;
+      };
+      if (vec) {
+        trips();
+      } else {
+        for (int64_t r = r_begin + ty; r < r_end; r += rows_per_pass) {  // scalar path
+          f32x8 a, y;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int c = cv * 8 + j;
-          a.v[j] = c < p.C ? (float)p.a[r * p.ld_a + c] : 0.f;
-          if (MODE == 1 || MODE == 3) y.v[j] = c < p.C ? (float)p.y[r * p.ld_y + c] : 0.f;
-          if constexpr (MODE == 3) {
-            if (c < p.C) {
-              const h16_t dq = (h16_t)(a.v[j] * act_bwd((float)p.z[r * p.ld_z + c], ACT, p.ap));
-              p.du[r * p.ld_du + c] = dq;
-              a.v[j] = (float)dq;
+          for (int j = 0; j < 8; ++j) {
+            const int c = cv * 8 + j;
+            a.v[j] = c < p.C ? (float)p.a[r * p.ld_a + c] : 0.f;
+            if (MODE == 1 || MODE == 3) y.v[j] = c < p.C ? (float)p.y[r * p.ld_y + c] : 0.f;
+            if constexpr (MODE == 3) {
+              if (c < p.C) {
+                const h16_t dq = (h16_t)(a.v[j] * act_bwd((float)p.z[r * p.ld_z + c], ACT, p.ap));
+                p.du[r * p.ld_du + c] = dq;
+                a.v[j] = (float)dq;
+              }
             }
           }
+          accum(a, y);
         }
-        accum(a, y);
       }
     }
     // reduce over ty through LDS
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      red[t * 16 + j] = s1[j];
-      red[t * 16 + 8 + j] = s2[j];
+      red[t * 16 + j] = s1[j >> 1][j & 1];
+      red[t * 16 + 8 + j] = s2[j >> 1][j & 1];
     }
     __syncthreads();
     // thread (tx, j16) sums over ty
@@ -365,6 +426,7 @@ struct EwParams {
   // RLZ instances (round 5, lazy activations): `res` is the RAW convolution output of the layer that produced the residual; the
   // pass applies that layer's BatchNorm scale / shift and the (same) activation to it on load: out = act(a*sc+sh) + act(res*rsc+rsh)
   const float *res_scale, *res_shift;
+  int addr32;  // a block's rows times the pitch fit 31 bits for every operand: 32-bit lane offsets (set by ew_set_addr32)
 };
 constexpr int kEwAccMaxC = 2048;
 
@@ -384,7 +446,8 @@ struct EW_RPT {
 // MODE 1: out = dy from (a = dz, y)               [BN+act backward apply]
 // MODE 2: out = a (copy)       MODE 3: out = a + res
 // RLZ (MODE 0 only): the residual operand is a LAZY activation — see EwParams::res_scale
-template <int MODE, int ACT = 0, bool ACC = false, bool RLZ = false>
+// A32: as for colreduce_kernel (EwParams::addr32)
+template <int MODE, int ACT = 0, bool ACC = false, bool RLZ = false, bool A32 = true>
 __global__ __launch_bounds__(256) void ew_kernel(const EwParams p) {
   static_assert(!RLZ || MODE == 0, "lazy residuals exist in the forward apply pass only");
   __shared__ float cst[ACC ? 2 * kEwAccMaxC : 1];  // ACC: MODE 0 scale | shift; MODE 1 dbeta/M | dgamma/M
@@ -516,45 +579,114 @@ __global__ __launch_bounds__(256) void ew_kernel(const EwParams p) {
         return o;
       };
       constexpr bool has_res = RES != 0;
-      int64_t r = r_begin + ty;
-      if (vec) {
-        // 4 rows per trip: all loads of the trip are issued before the arithmetic (bytes in flight per lane x4); the block's last
-        // trip runs the same code with its missing rows masked (clamped loads, no store) instead of a row-at-a-time remainder
-        const int64_t stp = rows_per_pass;
+      // 4 rows per trip: all loads of the trip are issued before the arithmetic (bytes in flight per lane x4); the block's last
+      // trip runs the same code with its missing rows masked (clamped loads, no store) instead of a row-at-a-time remainder.
+      // Addresses as in colreduce_kernel: block-uniform bases, per-lane byte offsets of type OFF advanced by a loop-invariant stride.
+      auto trips = [&](auto stats_tag) {
+        using OFF = std::conditional_t<A32, uint32_t, int64_t>;
+        constexpr bool STATS = decltype(stats_tag)::value;  // MODE 1: the batch-statistics terms are present (p.mean)
+        const int64_t left = r_end - r_begin;
+        const OFF nr = (OFF)(left > 0 ? left : 0);
+        const OFF stp = (OFF)rows_per_pass;
         constexpr int RPT = EW_RPT<MODE, has_res>::value;
-        for (; r < r_end; r += RPT * stp) {
+        const char* ab = reinterpret_cast<const char*>(p.a + r_begin * p.ld_a);
+        const char* yb = reinterpret_cast<const char*>(p.y + (MODE == 1 ? r_begin * p.ld_y : 0));
+        const char* rb = reinterpret_cast<const char*>(p.res + (has_res ? r_begin * p.ld_res : 0));
+        char* ob = reinterpret_cast<char*>(p.out + r_begin * p.ld_out);
+        const OFF da = stp * (OFF)p.ld_a * 2, dy = stp * (OFF)p.ld_y * 2, dr = stp * (OFF)p.ld_res * 2, dout = stp * (OFF)p.ld_out * 2;
+        OFF oa = ((OFF)ty * (OFF)p.ld_a + (OFF)c) * 2, oy = ((OFF)ty * (OFF)p.ld_y + (OFF)c) * 2;
+        OFF ores = ((OFF)ty * (OFF)p.ld_res + (OFF)c) * 2, oo = ((OFF)ty * (OFF)p.ld_out + (OFF)c) * 2;
+        f32x2 sc2[4], sh2[4], mu2[4], is2[4], k12[4], k22[4], rsc2[4], rsh2[4];
+        pairs_of(sc, sc2);
+        pairs_of(sh, sh2);
+        pairs_of(mu, mu2);
+        pairs_of(is, is2);
+        pairs_of(k1, k12);
+        pairs_of(k2, k22);
+        if constexpr (RLZ) {
+          pairs_of(rsc, rsc2);
+          pairs_of(rsh, rsh2);
+        }
+        for (OFF rr = (OFF)ty; rr < nr; rr += RPT * stp) {
           uint4 ua[RPT], uy[RPT], ur[RPT];
           bool ok[RPT];
 #pragma unroll
           for (int q = 0; q < RPT; ++q) {
-            const int64_t rq = r + q * stp;
-            ok[q] = rq < r_end;
-            const int64_t rc = ok[q] ? rq : r;
-            ua[q] = *reinterpret_cast<const uint4*>(p.a + rc * p.ld_a + c);
-            if (MODE == 1) uy[q] = *reinterpret_cast<const uint4*>(p.y + rc * p.ld_y + c);
-            if (has_res) ur[q] = *reinterpret_cast<const uint4*>(p.res + rc * p.ld_res + c);
+            ok[q] = rr + (OFF)q * stp < nr;
+            if constexpr (A32) {
+              ua[q] = *reinterpret_cast<const uint4*>(ab + (ok[q] ? oa + (OFF)q * da : oa));
+              if (MODE == 1) uy[q] = *reinterpret_cast<const uint4*>(yb + (ok[q] ? oy + (OFF)q * dy : oy));
+              if (has_res) ur[q] = *reinterpret_cast<const uint4*>(rb + (ok[q] ? ores + (OFF)q * dr : ores));
+            } else {  // 64-bit: the row's address from its index, every trip
+              const int64_t rc = r_begin + (ok[q] ? rr + (OFF)q * stp : rr);
+              ua[q] = *reinterpret_cast<const uint4*>(p.a + rc * p.ld_a + c);
+              if (MODE == 1) uy[q] = *reinterpret_cast<const uint4*>(p.y + rc * p.ld_y + c);
+              if (has_res) ur[q] = *reinterpret_cast<const uint4*>(p.res + rc * p.ld_res + c);
+            }
           }
           __builtin_amdgcn_sched_barrier(0);  // loads of all rows of the trip first (see colreduce_kernel)
 #pragma unroll
           for (int q = 0; q < RPT; ++q) {
-            const f32x8 o = math(unpack8(ua[q]), MODE == 1 ? unpack8(uy[q]) : f32x8{}, has_res ? unpack8(ur[q]) : f32x8{});
-            if (ok[q]) *reinterpret_cast<uint4*>(p.out + (r + q * stp) * p.ld_out + c) = pack8(o);
+            uint4 packed;
+            if constexpr (MODE == 0) {
+              f32x2 a[4], rs[4], o[4];
+              unpack_pairs(ua[q], a);
+              if (has_res) unpack_pairs(ur[q], rs);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                f32x2 r2 = has_res ? rs[k] : f32x2{0.f, 0.f};
+                if constexpr (RES == 3) {  // the lazy residual, rounded as the stand-alone pass stores it
+                  const f32x2 v = act_fwd2<ACT, false>(fma2(rs[k], rsc2[k], rsh2[k]), p.ap, f32x2{0.f, 0.f});
+                  r2 = unpack_pair(pack2(v.x, v.y));
+                }
+                o[k] = bnact_fwd2<ACT, RES == 3 ? 1 : RES>(a[k], sc2[k], sh2[k], r2, p.ap);
+              }
+              packed = pack_pairs(o);
+            } else if constexpr (MODE == 1) {
+              f32x2 d[4], yy[4], o[4];
+              unpack_pairs(ua[q], d);
+              unpack_pairs(uy[q], yy);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) o[k] = bnact_bwd_apply2<ACT, STATS>(d[k], yy[k], sc2[k], sh2[k], mu2[k], is2[k], k12[k], k22[k], p.ap);
+              packed = pack_pairs(o);
+            } else {
+              packed = pack8(math(unpack8(ua[q]), f32x8{}, has_res ? unpack8(ur[q]) : f32x8{}));
+            }
+            if (ok[q]) {
+              if constexpr (A32) *reinterpret_cast<uint4*>(ob + (oo + (OFF)q * dout)) = packed;
+              else *reinterpret_cast<uint4*>(p.out + (r_begin + rr + (OFF)q * stp) * p.ld_out + c) = packed;
+            }
+          }
+          if constexpr (A32) {
+            oa += RPT * da;
+            if (MODE == 1) oy += RPT * dy;
+            if (has_res) ores += RPT * dr;
+            oo += RPT * dout;
           }
         }
-      }
-      for (; r < r_end; r += rows_per_pass) {  // (scalar path only)
-        f32x8 a, y, rs;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool okc = c + j < p.C;
-          a.v[j] = okc ? (float)p.a[r * p.ld_a + c + j] : 0.f;
-          if (MODE == 1) y.v[j] = okc ? (float)p.y[r * p.ld_y + c + j] : 0.f;
-          if (has_res) rs.v[j] = okc ? (float)p.res[r * p.ld_res + c + j] : 0.f;
+      };
+      if (vec) {
+        bool stats = false;
+        if constexpr (MODE == 1) stats = p.mean != nullptr;
+        if constexpr (MODE == 1) {
+          if (stats) trips(std::true_type{});
         }
-        const f32x8 o = math(a, y, rs);
+        if (!stats) trips(std::false_type{});
+      } else {
+        for (int64_t r = r_begin + ty; r < r_end; r += rows_per_pass) {  // scalar path
+          f32x8 a, y, rs;
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (c + j < p.C) p.out[r * p.ld_out + c + j] = (h16_t)o.v[j];
+          for (int j = 0; j < 8; ++j) {
+            const bool okc = c + j < p.C;
+            a.v[j] = okc ? (float)p.a[r * p.ld_a + c + j] : 0.f;
+            if (MODE == 1) y.v[j] = okc ? (float)p.y[r * p.ld_y + c + j] : 0.f;
+            if (has_res) rs.v[j] = okc ? (float)p.res[r * p.ld_res + c + j] : 0.f;
+          }
+          const f32x8 o = math(a, y, rs);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (c + j < p.C) p.out[r * p.ld_out + c + j] = (h16_t)o.v[j];
+        }
       }
     };
     if constexpr (RLZ) {
@@ -601,27 +733,57 @@ __global__ __launch_bounds__(256) void bn_finalize_acc_kernel(const double* acc,
 // blocks are row chunks; a thread moves 16 B per row visit, so ~32 row-visits per thread keeps
 // enough bytes in flight while leaving >> 256 blocks for large activations
 // launch KERNEL<MODE, act> for the runtime activation id
-#define CVHIP_LAUNCH_ACT_ACC(KERNEL, MODE, ACTV, GRID, STREAM, PARAMS)                                                         \
-  switch (ACTV) {                                                                                                              \
-    case CVHIP_ACT_RELU: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_RELU, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;        \
-    case CVHIP_ACT_SILU: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_SILU, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;        \
-    case CVHIP_ACT_LEAKY: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_LEAKY, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;      \
-    case CVHIP_ACT_SIGMOID: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_SIGMOID, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;  \
-    case CVHIP_ACT_HSWISH: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_HSWISH, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;    \
-    default: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_NONE, true>), GRID, dim3(256), 0, STREAM, PARAMS); break;                   \
+// launch the A32 or the 64-bit instance of a kernel, as the host found for this launch (PARAMS.addr32)
+#define CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, ...)                                                     \
+  do {                                                                                                          \
+    if ((PARAMS).addr32) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true>), GRID, dim3(256), 0, STREAM, PARAMS);   \
+    else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false>), GRID, dim3(256), 0, STREAM, PARAMS);                  \
+  } while (0)
+
+#define CVHIP_LAUNCH_ACT_ACC(KERNEL, MODE, ACTV, GRID, STREAM, PARAMS)                                              \
+  switch (ACTV) {                                                                                                   \
+    case CVHIP_ACT_RELU: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_RELU, true, false); break;       \
+    case CVHIP_ACT_SILU: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_SILU, true, false); break;       \
+    case CVHIP_ACT_LEAKY: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_LEAKY, true, false); break;     \
+    case CVHIP_ACT_SIGMOID: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_SIGMOID, true, false); break; \
+    case CVHIP_ACT_HSWISH: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_HSWISH, true, false); break;   \
+    default: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_NONE, true, false); break;                  \
   }
 
-#define CVHIP_LAUNCH_ACT(KERNEL, MODE, ACTV, GRID, STREAM, PARAMS)                                                       \
-  switch (ACTV) {                                                                                                        \
-    case CVHIP_ACT_RELU: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_RELU>), GRID, dim3(256), 0, STREAM, PARAMS); break;        \
-    case CVHIP_ACT_SILU: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_SILU>), GRID, dim3(256), 0, STREAM, PARAMS); break;        \
-    case CVHIP_ACT_LEAKY: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_LEAKY>), GRID, dim3(256), 0, STREAM, PARAMS); break;      \
-    case CVHIP_ACT_SIGMOID: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_SIGMOID>), GRID, dim3(256), 0, STREAM, PARAMS); break;  \
-    case CVHIP_ACT_HSWISH: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_HSWISH>), GRID, dim3(256), 0, STREAM, PARAMS); break;    \
-    default: hipLaunchKernelGGL((KERNEL<MODE, CVHIP_ACT_NONE>), GRID, dim3(256), 0, STREAM, PARAMS); break;                   \
+// TAIL: the template arguments between the activation and A32 (ew_kernel: `false, false`; colreduce_kernel: none)
+#define CVHIP_LAUNCH_ACT(KERNEL, MODE, ACTV, GRID, STREAM, PARAMS, ...)                                               \
+  switch (ACTV) {                                                                                                     \
+    case CVHIP_ACT_RELU: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_RELU __VA_ARGS__); break;       \
+    case CVHIP_ACT_SILU: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_SILU __VA_ARGS__); break;       \
+    case CVHIP_ACT_LEAKY: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_LEAKY __VA_ARGS__); break;     \
+    case CVHIP_ACT_SIGMOID: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_SIGMOID __VA_ARGS__); break; \
+    case CVHIP_ACT_HSWISH: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_HSWISH __VA_ARGS__); break;   \
+    default: CVHIP_LAUNCH_A32(KERNEL, GRID, STREAM, PARAMS, MODE, CVHIP_ACT_NONE __VA_ARGS__); break;                  \
   }
+#define CVHIP_EW_PLAIN , false, false
 
 static int ew_rows_per_thread() { return 16; }   // (4 / 8 rows per thread lose 0.1-0.6 ms per step to the per-block prologue: profiles/r04_ew_grid_ab.log)
+
+// ((rows of a block) * pitch + C) 16-bit elements stay below 2^31 bytes: the lanes of a block can address the operand with 32-bit offsets
+static inline bool fits31(int64_t rows, int ld, int C) { return (rows * (int64_t)ld + C) * 2 < ((int64_t)1 << 31); }
+
+static inline int ew_grid(int64_t M, int C);
+// the grid of an elementwise launch; sets p.addr32 for it
+static inline dim3 ew_dims(EwParams& p) {
+  const int grid = ew_grid(p.M, p.C);
+  const int64_t rows = cdiv64(p.M, grid);
+  p.addr32 = fits31(rows, p.ld_a, p.C) && fits31(rows, p.ld_out, p.C) && (!p.y || fits31(rows, p.ld_y, p.C)) &&
+             (!p.res || fits31(rows, p.ld_res, p.C));
+  return dim3(grid);
+}
+// the grid of a column-reduction launch; sets p.addr32 for it
+static inline dim3 red_dims(RedParams& p) {
+  const int grid = colreduce_rows_host(p.M, p.C);
+  const int64_t rows = cdiv64(p.M, grid);
+  p.addr32 = fits31(rows, p.ld_a, p.C) && (!p.y || fits31(rows, p.ld_y, p.C)) && (!p.z || fits31(rows, p.ld_z, p.C)) &&
+             (!p.du || fits31(rows, p.ld_du, p.C));
+  return dim3(grid);
+}
 
 static inline int ew_grid(int64_t M, int C) {
   const int CV = (C + 7) / 8;
@@ -643,12 +805,12 @@ int cvhip_colreduce_rows(int64_t M, int32_t C) { return colreduce_rows_host(M, C
 
 static int launch_red(int mode, RedParams& p, hipStream_t s) {
   if (!p.a || !p.partial || p.M < 0 || p.C <= 0) return CVHIP_ERR_INVALID;
-  const int rows = colreduce_rows_host(p.M, p.C);
-  if (mode == 0) hipLaunchKernelGGL(colreduce_kernel<0>, dim3(rows), dim3(256), 0, s, p);
+  const dim3 grid = red_dims(p);
+  if (mode == 0) CVHIP_LAUNCH_A32(colreduce_kernel, grid, s, p, 0, 0);
   else if (mode == 1) {
-    CVHIP_LAUNCH_ACT(colreduce_kernel, 1, p.act, dim3(rows), s, p)
+    CVHIP_LAUNCH_ACT(colreduce_kernel, 1, p.act, grid, s, p)
   }
-  else hipLaunchKernelGGL(colreduce_kernel<2>, dim3(rows), dim3(256), 0, s, p);
+  else CVHIP_LAUNCH_A32(colreduce_kernel, grid, s, p, 2, 0);
   return check_launch("colreduce_kernel");
 }
 
@@ -758,7 +920,8 @@ int cvhip_bn_act_fwd(const void* y, int32_t ld_y, void* z, int32_t ld_z, int64_t
   p.shift = shift;
   p.act = act;
   p.ap = act_param;
-  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, grid, (hipStream_t)stream, p, CVHIP_EW_PLAIN)
   return check_launch("ew_kernel<0>");
 }
 
@@ -780,7 +943,8 @@ int cvhip_bn_add_act_fwd(const void* y, int32_t ld_y, void* z, int32_t ld_z, int
   p.act = act;
   p.ap = act_param;
   p.res_pre = 1;  // the residual joins BEFORE the activation
-  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, grid, (hipStream_t)stream, p, CVHIP_EW_PLAIN)
   return check_launch("ew_kernel<0>(bn_add_act)");
 }
 
@@ -809,7 +973,8 @@ int cvhip_bn_act_bwd_apply(const void* dz, int32_t ld_dz, const void* y, int32_t
   p.act = act;
   p.ap = act_param;
   p.inv_count = 1.f / (float)M;
-  CVHIP_LAUNCH_ACT(ew_kernel, 1, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT(ew_kernel, 1, act, grid, (hipStream_t)stream, p, CVHIP_EW_PLAIN)
   return check_launch("ew_kernel<1>");
 }
 
@@ -829,7 +994,8 @@ int cvhip_add_act_fwd(const void* a, int32_t ld_a, const void* b, int32_t ld_b, 
   p.act = act;
   p.ap = act_param;
   p.res_pre = 1;
-  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT(ew_kernel, 0, act, grid, (hipStream_t)stream, p, CVHIP_EW_PLAIN)
   return check_launch("ew_kernel<0>(add_act)");
 }
 
@@ -843,7 +1009,8 @@ int cvhip_copy2d(const void* src, int32_t ld_src, void* dst, int32_t ld_dst, int
   p.ld_out = ld_dst;
   p.M = M;
   p.C = C;
-  hipLaunchKernelGGL(ew_kernel<2>, dim3(ew_grid(M, C)), dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_A32(ew_kernel, grid, (hipStream_t)stream, p, 2, 0, false, false);
   return check_launch("ew_kernel<2>");
 }
 
@@ -860,7 +1027,8 @@ int cvhip_add2d(const void* a, int32_t ld_a, const void* b, int32_t ld_b, void* 
   p.ld_out = ld_dst;
   p.M = M;
   p.C = C;
-  hipLaunchKernelGGL(ew_kernel<3>, dim3(ew_grid(M, C)), dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_A32(ew_kernel, grid, (hipStream_t)stream, p, 3, 0, false, false);
   return check_launch("ew_kernel<3>");
 }
 
@@ -886,8 +1054,8 @@ int cvhip_bn_act_bwd_sums_acc(const void* dz, int32_t ld_dz, const void* y, int3
   p.ap = act_param;
   p.acc = acc;
   p.acc_ld = acc_ld;
-  const int rows = colreduce_rows_host(M, C);
-  CVHIP_LAUNCH_ACT(colreduce_kernel, 1, act, dim3(rows), (hipStream_t)stream, p)
+  const dim3 grid = red_dims(p);
+  CVHIP_LAUNCH_ACT(colreduce_kernel, 1, act, grid, (hipStream_t)stream, p)
   return check_launch("colreduce_kernel(acc)");
 }
 
@@ -914,11 +1082,11 @@ int cvhip_bn_tail_bwd_sums_acc(const void* dz, int32_t ld_dz, const void* z_out,
   p.ap = act_param;
   p.acc = acc;
   p.acc_ld = acc_ld;
-  const int rows = colreduce_rows_host(M, C);
+  const dim3 grid = red_dims(p);
   switch (act) {
-    case CVHIP_ACT_RELU: hipLaunchKernelGGL((colreduce_kernel<3, CVHIP_ACT_RELU>), dim3(rows), dim3(256), 0, (hipStream_t)stream, p); break;
-    case CVHIP_ACT_LEAKY: hipLaunchKernelGGL((colreduce_kernel<3, CVHIP_ACT_LEAKY>), dim3(rows), dim3(256), 0, (hipStream_t)stream, p); break;
-    default: hipLaunchKernelGGL((colreduce_kernel<3, CVHIP_ACT_NONE>), dim3(rows), dim3(256), 0, (hipStream_t)stream, p); break;
+    case CVHIP_ACT_RELU: CVHIP_LAUNCH_A32(colreduce_kernel, grid, (hipStream_t)stream, p, 3, CVHIP_ACT_RELU); break;
+    case CVHIP_ACT_LEAKY: CVHIP_LAUNCH_A32(colreduce_kernel, grid, (hipStream_t)stream, p, 3, CVHIP_ACT_LEAKY); break;
+    default: CVHIP_LAUNCH_A32(colreduce_kernel, grid, (hipStream_t)stream, p, 3, CVHIP_ACT_NONE); break;
   }
   return check_launch("colreduce_kernel<3>(acc)");
 }
@@ -954,7 +1122,8 @@ int cvhip_bn_act_fwd_acc(const void* y, int32_t ld_y, void* z, int32_t ld_z, int
   p.o_invstd = invstd;
   p.o_scale = scale;
   p.o_shift = shift;
-  CVHIP_LAUNCH_ACT_ACC(ew_kernel, 0, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT_ACC(ew_kernel, 0, act, grid, (hipStream_t)stream, p)
   return check_launch("ew_kernel<0,acc>");
 }
 
@@ -1001,11 +1170,11 @@ int cvhip_bn_act_fwd_acc_lazyres(const void* y, int32_t ld_y, void* z, int32_t l
   p.o_invstd = invstd;
   p.o_scale = scale;
   p.o_shift = shift;
-  const dim3 grid(ew_grid(M, C));
+  const dim3 grid = ew_dims(p);
   switch (act) {
-    case CVHIP_ACT_RELU: hipLaunchKernelGGL((ew_kernel<0, CVHIP_ACT_RELU, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p); break;
-    case CVHIP_ACT_SILU: hipLaunchKernelGGL((ew_kernel<0, CVHIP_ACT_SILU, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p); break;
-    case CVHIP_ACT_LEAKY: hipLaunchKernelGGL((ew_kernel<0, CVHIP_ACT_LEAKY, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p); break;
+    case CVHIP_ACT_RELU: CVHIP_LAUNCH_A32(ew_kernel, grid, (hipStream_t)stream, p, 0, CVHIP_ACT_RELU, true, true); break;
+    case CVHIP_ACT_SILU: CVHIP_LAUNCH_A32(ew_kernel, grid, (hipStream_t)stream, p, 0, CVHIP_ACT_SILU, true, true); break;
+    case CVHIP_ACT_LEAKY: CVHIP_LAUNCH_A32(ew_kernel, grid, (hipStream_t)stream, p, 0, CVHIP_ACT_LEAKY, true, true); break;
     default: return CVHIP_ERR_UNSUPPORTED;
   }
   return check_launch("ew_kernel<0,acc,lazyres>");
@@ -1037,7 +1206,8 @@ int cvhip_bn_act_bwd_apply_acc(const void* dz, int32_t ld_dz, const void* y, int
   p.o_dgamma = dgamma;
   p.o_dbeta = dbeta;
   p.accumulate = accumulate;
-  CVHIP_LAUNCH_ACT_ACC(ew_kernel, 1, act, dim3(ew_grid(M, C)), (hipStream_t)stream, p)
+  const dim3 grid = ew_dims(p);
+  CVHIP_LAUNCH_ACT_ACC(ew_kernel, 1, act, grid, (hipStream_t)stream, p)
   return check_launch("ew_kernel<1,acc>");
 }
 

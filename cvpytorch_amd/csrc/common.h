@@ -152,6 +152,129 @@ __device__ __forceinline__ void bnact_bwd8_into(const float (&dz)[8], const floa
   }
 }
 
+// ---- pair-wise forms (vector paths of bn_act.hip) ------------------------------------------------------------------------------------
+// The same arithmetic on two neighbouring channels at a time, written on a float ext-vector of 2 so that every row of a trip compiles
+// to v_pk_*_f32 (two elements per issue slot) instead of whatever mix of scalar and packed code the SLP vectorizer finds per row.
+// Every function runs with contraction OFF and spells its fused multiply-adds out: the set of roundings is part of the result (the
+// training step is bit-reproducible against earlier builds), so it is written down here instead of being left to the optimizer.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// one dword of two 16-bit values -> a pair (bf16: one shift, one and)
+__device__ __forceinline__ f32x2 unpack_pair(uint32_t w) {
+  float lo, hi;
+  unpack2(w, lo, hi);
+  return f32x2{lo, hi};
+}
+__device__ __forceinline__ void unpack_pairs(const uint4& u, f32x2 (&o)[4]) {
+  o[0] = unpack_pair(u.x);
+  o[1] = unpack_pair(u.y);
+  o[2] = unpack_pair(u.z);
+  o[3] = unpack_pair(u.w);
+}
+__device__ __forceinline__ uint4 pack_pairs(const f32x2 (&f)[4]) {
+  return make_uint4(pack2(f[0].x, f[0].y), pack2(f[1].x, f[1].y), pack2(f[2].x, f[2].y), pack2(f[3].x, f[3].y));
+}
+__device__ __forceinline__ void pairs_of(const float (&s)[8], f32x2 (&o)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = f32x2{s[2 * k], s[2 * k + 1]};
+}
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+
+// sigmoidf_ on a pair: x * (-log2 e) (the multiply __expf(-x) lowers to), v_exp_f32, 1 + e, v_rcp_f32
+__device__ __forceinline__ f32x2 sigmoid2(f32x2 x) {
+#pragma clang fp contract(off)
+  const f32x2 t = x * -1.44269504088896340736f;
+  const f32x2 e = 1.0f + f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+  return f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+}
+
+// act(u) (+ r when ADD: a residual that joins after the activation; the multiply that ends SiLU / h-swish is fused with that add)
+template <int ACT, bool ADD>
+__device__ __forceinline__ f32x2 act_fwd2(f32x2 u, float ap, f32x2 r) {
+#pragma clang fp contract(off)
+  if constexpr (ACT == CVHIP_ACT_SILU) {
+    const f32x2 s = sigmoid2(u);
+    return ADD ? fma2(u, s, r) : u * s;
+  } else if constexpr (ACT == CVHIP_ACT_HSWISH) {
+    const f32x2 t = u + 3.f;
+    const f32x2 w = u * f32x2{fminf(fmaxf(t.x, 0.f), 6.f), fminf(fmaxf(t.y, 0.f), 6.f)};
+    return ADD ? fma2(w, f32x2{1.f / 6.f, 1.f / 6.f}, r) : w * (1.f / 6.f);
+  } else {
+    f32x2 v = u;
+    if constexpr (ACT == CVHIP_ACT_RELU) v = f32x2{u.x > 0.f ? u.x : 0.f, u.y > 0.f ? u.y : 0.f};
+    if constexpr (ACT == CVHIP_ACT_LEAKY) {
+      const f32x2 n = u * ap;
+      v = f32x2{u.x > 0.f ? u.x : n.x, u.y > 0.f ? u.y : n.y};
+    }
+    if constexpr (ACT == CVHIP_ACT_SIGMOID) v = sigmoid2(u);
+    return ADD ? v + r : v;
+  }
+}
+
+// act'(u)
+template <int ACT>
+__device__ __forceinline__ f32x2 act_bwd2(f32x2 u, float ap) {
+#pragma clang fp contract(off)
+  if constexpr (ACT == CVHIP_ACT_RELU) {
+    return f32x2{u.x > 0.f ? 1.f : 0.f, u.y > 0.f ? 1.f : 0.f};
+  } else if constexpr (ACT == CVHIP_ACT_SILU) {
+    const f32x2 s = sigmoid2(u);
+    return s * fma2(u, 1.f - s, f32x2{1.f, 1.f});
+  } else if constexpr (ACT == CVHIP_ACT_LEAKY) {
+    return f32x2{u.x > 0.f ? 1.f : ap, u.y > 0.f ? 1.f : ap};
+  } else if constexpr (ACT == CVHIP_ACT_SIGMOID) {
+    const f32x2 s = sigmoid2(u);
+    return s * (1.f - s);
+  } else if constexpr (ACT == CVHIP_ACT_HSWISH) {
+    const f32x2 m = fma2(u, f32x2{2.f, 2.f}, f32x2{3.f, 3.f}) * (1.f / 6.f);
+    return f32x2{u.x <= -3.f ? 0.f : (u.x >= 3.f ? 1.f : m.x), u.y <= -3.f ? 0.f : (u.y >= 3.f ? 1.f : m.y)};
+  } else {
+    return f32x2{1.f, 1.f};
+  }
+}
+
+// BN + activation forward of a pair: act(a*sc + sh [+ r]) [+ r]. RES 0: no residual, 1: added after the activation, 2: before it
+template <int ACT, int RES>
+__device__ __forceinline__ f32x2 bnact_fwd2(f32x2 a, f32x2 sc, f32x2 sh, f32x2 r, float ap) {
+#pragma clang fp contract(off)
+  f32x2 u = fma2(a, sc, sh);
+  if constexpr (RES == 2) u = u + r;
+  return act_fwd2<ACT, RES == 1>(u, ap, r);
+}
+
+// BN-backward sums of a pair: s1 += du, s2 += du * xhat with du = dz * act'(y*sc + sh), xhat = (y - mu) * is.
+// FUSE1: s1 takes the product fused (fma(act', dz, s1)) instead of the rounded du; the caller says which (colreduce_kernel keeps, row
+// by row, the form each row has always had, so that the sums stay what they were bit for bit).
+template <int ACT, bool FUSE1>
+__device__ __forceinline__ void bnact_bwd_sums2(f32x2 dz, f32x2 y, f32x2 sc, f32x2 sh, f32x2 mu, f32x2 is, float ap, f32x2& s1, f32x2& s2) {
+#pragma clang fp contract(off)
+  const f32x2 ad = act_bwd2<ACT>(fma2(y, sc, sh), ap);
+  const f32x2 du = ad * dz;
+  const f32x2 xh = (y - mu) * is;
+  s1 = FUSE1 ? fma2(ad, dz, s1) : s1 + du;
+  s2 = fma2(du, xh, s2);
+}
+// the residual-tail form: du is given (already rounded to 16 bits), the BatchNorm branch has no activation of its own
+__device__ __forceinline__ void bn_bwd_sums2(f32x2 du, f32x2 y, f32x2 mu, f32x2 is, f32x2& s1, f32x2& s2) {
+#pragma clang fp contract(off)
+  const f32x2 xh = (y - mu) * is;
+  s1 = s1 + du;
+  s2 = fma2(du, xh, s2);
+}
+
+// BN + activation backward apply of a pair: sc * (du - k1 - xhat*k2) (k1 = dbeta/M, k2 = dgamma/M), or sc * du without statistics
+template <int ACT, bool HAS_STATS>
+__device__ __forceinline__ f32x2 bnact_bwd_apply2(f32x2 dz, f32x2 y, f32x2 sc, f32x2 sh, f32x2 mu, f32x2 is, f32x2 k1, f32x2 k2, float ap) {
+#pragma clang fp contract(off)
+  const f32x2 ad = act_bwd2<ACT>(fma2(y, sc, sh), ap);
+  if constexpr (!HAS_STATS) {
+    return sc * (ad * dz);
+  } else {
+    const f32x2 xh = (y - mu) * is;
+    return sc * fma2(-xh, k2, fma2(ad, dz, -k1));
+  }
+}
+
 // 8 per-channel constants for the channel vector starting at c: UNCONDITIONAL clamped loads (a per-element
 // `ok ? p[c] : dflt` compiles to 8 exec-masked blocks with an s_waitcnt vmcnt(0) at every join: 16-48 serialized
 // ~1 us round trips per thread, i.e. a fixed ~17 us per launch — measured, tools/stream_probe.py)
