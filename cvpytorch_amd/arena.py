@@ -522,9 +522,19 @@ class FlatTrainState(BucketSchedule):
             L.call("cvhip_sgd_nesterov_ema", self.param.data_ptr(), self.grad.data_ptr(), self.mom.data_ptr(), ema_ptr, self.total,
                    self.seg_bounds.data_ptr(), self.seg_lr.data_ptr(), self.seg_wd.data_ptr(), len(self.params), self.momentum,
                    int(self.nesterov), 0, 0.0, 1.0 / self.world, self.dyn.data_ptr(), st)
-        if self.ema_buf is not None and self.buf.numel():
+        n_ema = self.buf.numel() if self.ema_buf is not None else 0
+        n_nbt = self._nbt.numel() if (self._nbt is not None and self.model.training) else 0
+        if hasattr(L.load(), "cvhip_train_step_tail"):   # (absent only from an older build under A/B through CVHIP_LIB)
+            # EMA of the BN statistics, the BN step counters, zero_grad and zero_stats: one launch
+            L.call("cvhip_train_step_tail", self.ema_buf.data_ptr() if n_ema else None, self.buf.data_ptr() if n_ema else None, n_ema, 0.0,
+                   self.dyn.data_ptr(), self._nbt.data_ptr() if n_nbt else None, n_nbt, 1, self.grad.data_ptr(),
+                   self.grad.numel() * self.grad.element_size(), self.stat_acc.data_ptr() if self.stat_acc.numel() else None,
+                   self.stat_acc.numel() * self.stat_acc.element_size(), st)
+            self._acc_epoch[0] += 1
+            return
+        if n_ema:
             L.call("cvhip_ema_update", self.ema_buf.data_ptr(), self.buf.data_ptr(), self.buf.numel(), 0.0, self.dyn.data_ptr(), st)
-        if self._nbt is not None and self.model.training:
+        if n_nbt:
             L.call("cvhip_i64_add", self._nbt.data_ptr(), self._nbt.numel(), 1, st)
         self.zero_grad()
         self.zero_stats()

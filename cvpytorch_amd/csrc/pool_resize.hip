@@ -172,30 +172,16 @@ static inline int pool_lds_cvb(int HW, bool bwd) {   // the widest block that fi
   return 0;
 }
 
+// The two passes of one k x k stage as device functions over the block's LDS image: the single-pool kernel runs them once, the SPPF
+// chain kernel (sppf_chain_fwd_kernel) three times, each stage reading the values the stage before left in `xs`.
+// pass 1: every (pixel, channel vector) scans its ROW window (the values are 16-bit inputs, -inf or NaN: pack8 keeps them exactly)
 template <int K, int kPoolLdsCvb>
-__global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
-  const int CV = p.C >> 3;
-  const int groups = (CV + kPoolLdsCvb - 1) / kPoolLdsCvb;
-  const int n = blockIdx.x / groups, cv0 = (blockIdx.x - n * groups) * kPoolLdsCvb;
-  const int cvb = min(kPoolLdsCvb, CV - cv0);
-  const int HW = p.H * p.W;
-  const int items = HW * kPoolLdsCvb;
-  uint4* const xs = reinterpret_cast<uint4*>(pool_smem);                       // [H*W][CVB] input vectors
-  uint4* const rvs = xs + items;                                               // [H*W][CVB] ROW results: value of the row's first maximum
-  uint2* const rks = reinterpret_cast<uint2*>(rvs + items);                    // ... and its kw, one byte per channel
-  const h16_t* const xn = p.x + (int64_t)n * HW * p.ld_x + cv0 * 8;
-  for (int i = threadIdx.x; i < items; i += 256) {
-    const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
-    if (cv < cvb) xs[i] = *reinterpret_cast<const uint4*>(xn + (int64_t)pix * p.ld_x + cv * 8);
-  }
-  __syncthreads();
+__device__ __forceinline__ void pool_lds_row_pass(const uint4* xs, uint4* rvs, uint2* rks, const int items, const int cvb, const int W) {
   constexpr int PAD = K / 2;
-  // pass 1: every (pixel, channel vector) scans its ROW window (the values are 16-bit inputs, -inf or NaN: pack8 keeps them exactly)
   for (int i = threadIdx.x; i < items; i += 256) {
     const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
     if (cv >= cvb) continue;
-    const int h = pix / p.W, w = pix - h * p.W;
+    const int h = pix / W, w = pix - h * W;
     f32x8 ov;
     int ok[8];
     bool first = true;
@@ -207,8 +193,8 @@ __global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParam
 #pragma unroll
     for (int kw = 0; kw < K; ++kw) {
       const int iw = w + kw - PAD;
-      if ((unsigned)iw >= (unsigned)p.W) continue;
-      const f32x8 v = unpack8(xs[(h * p.W + iw) * kPoolLdsCvb + cv]);
+      if ((unsigned)iw >= (unsigned)W) continue;
+      const f32x8 v = unpack8(xs[(h * W + iw) * kPoolLdsCvb + cv]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (first) ok[j] = kw;
@@ -225,12 +211,18 @@ __global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParam
     kk.y = (unsigned)ok[4] | ((unsigned)ok[5] << 8) | ((unsigned)ok[6] << 16) | ((unsigned)ok[7] << 24);
     rks[i] = kk;
   }
-  __syncthreads();
-  // pass 2: combine the row results top to bottom
+}
+
+// pass 2: combine the row results top to bottom. yn / idxn: the image's first pixel at the block's first channel vector (idxn may be
+// null); KEEP: also leave the packed values in `xs` for a following stage (pass 2 reads only the row results, so in place is safe)
+template <int K, int kPoolLdsCvb, bool KEEP>
+__device__ __forceinline__ void pool_lds_col_pass(const uint4* rvs, const uint2* rks, uint4* xs, const int items, const int cvb, const int H,
+                                                  const int W, h16_t* yn, const int ld_y, uint8_t* idxn, const int C) {
+  constexpr int PAD = K / 2;
   for (int i = threadIdx.x; i < items; i += 256) {
     const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
     if (cv >= cvb) continue;
-    const int h = pix / p.W, w = pix - h * p.W;
+    const int h = pix / W, w = pix - h * W;
     float best[8];
     int bi[8];
     bool first = true;
@@ -242,8 +234,8 @@ __global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParam
 #pragma unroll
     for (int kh = 0; kh < K; ++kh) {
       const int ih = h + kh - PAD;
-      if ((unsigned)ih >= (unsigned)p.H) continue;
-      const int o = (ih * p.W + w) * kPoolLdsCvb + cv;
+      if ((unsigned)ih >= (unsigned)H) continue;
+      const int o = (ih * W + w) * kPoolLdsCvb + cv;
       const f32x8 v = unpack8(rvs[o]);
       const uint2 kk = rks[o];
 #pragma unroll
@@ -258,23 +250,111 @@ __global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParam
       first = false;
     }
     {
-      const int64_t opix = (int64_t)n * HW + h * p.W + w;
       f32x8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) o.v[j] = best[j];
-      *reinterpret_cast<uint4*>(p.y + opix * p.ld_y + (cv0 + cv) * 8) = pack8(o);
-      if (p.idx) {
+      const uint4 packed = pack8(o);
+      *reinterpret_cast<uint4*>(yn + (int64_t)pix * ld_y + cv * 8) = packed;
+      if (KEEP) xs[i] = packed;
+      if (idxn) {
         uint2 iv;
         iv.x = (unsigned)bi[0] | ((unsigned)bi[1] << 8) | ((unsigned)bi[2] << 16) | ((unsigned)bi[3] << 24);
         iv.y = (unsigned)bi[4] | ((unsigned)bi[5] << 8) | ((unsigned)bi[6] << 16) | ((unsigned)bi[7] << 24);
-        *reinterpret_cast<uint2*>(p.idx + opix * p.C + (cv0 + cv) * 8) = iv;
+        *reinterpret_cast<uint2*>(idxn + (int64_t)pix * C + cv * 8) = iv;
       }
     }
   }
 }
 
+// the block's image x channel-vector group: [H*W][CVB] 16-byte vectors of one image, staged with coalesced row pieces
+template <int kPoolLdsCvb>
+__device__ __forceinline__ void pool_lds_stage(uint4* xs, const h16_t* xn, const int ld_x, const int items, const int cvb) {
+  for (int i = threadIdx.x; i < items; i += 256) {
+    const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
+    if (cv < cvb) xs[i] = *reinterpret_cast<const uint4*>(xn + (int64_t)pix * ld_x + cv * 8);
+  }
+}
+
+template <int K, int kPoolLdsCvb>
+__global__ __launch_bounds__(256) void maxpool_s1_lds_fwd_kernel(const PoolParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
+  const int CV = p.C >> 3;
+  const int groups = (CV + kPoolLdsCvb - 1) / kPoolLdsCvb;
+  const int n = blockIdx.x / groups, cv0 = (blockIdx.x - n * groups) * kPoolLdsCvb;
+  const int cvb = min(kPoolLdsCvb, CV - cv0);
+  const int HW = p.H * p.W;
+  const int items = HW * kPoolLdsCvb;
+  uint4* const xs = reinterpret_cast<uint4*>(pool_smem);                       // [H*W][CVB] input vectors
+  uint4* const rvs = xs + items;                                               // [H*W][CVB] ROW results: value of the row's first maximum
+  uint2* const rks = reinterpret_cast<uint2*>(rvs + items);                    // ... and its kw, one byte per channel
+  pool_lds_stage<kPoolLdsCvb>(xs, p.x + (int64_t)n * HW * p.ld_x + cv0 * 8, p.ld_x, items, cvb);
+  __syncthreads();
+  pool_lds_row_pass<K, kPoolLdsCvb>(xs, rvs, rks, items, cvb, p.W);
+  __syncthreads();
+  pool_lds_col_pass<K, kPoolLdsCvb, false>(rvs, rks, xs, items, cvb, p.H, p.W, p.y + (int64_t)n * HW * p.ld_y + cv0 * 8, p.ld_y,
+                                           p.idx ? p.idx + (int64_t)n * HW * p.C + cv0 * 8 : nullptr, p.C);
+}
+
+// SPPF's chain x -> m(x) -> m(m(x)) -> m(m(m(x))) in ONE launch: slice 0 of the (N, 4c, H, W) buffer is staged once, every stage runs
+// out of the LDS (its values replace the stage's input there), writes its values to slice j + 1 and its arg-max bytes to idx[j]. The
+// same two passes as the single pool, so values and arg-max bytes are those of three maxpool_s1_lds_fwd_kernel launches; LDS per item
+// as for one pool (40 bytes).
+template <int K, int kPoolLdsCvb>
+__global__ __launch_bounds__(256) void sppf_chain_fwd_kernel(h16_t* __restrict__ buf, const int ld, uint8_t* __restrict__ idx, const int N,
+                                                             const int c, const int H, const int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
+  const int CV = c >> 3;
+  const int groups = (CV + kPoolLdsCvb - 1) / kPoolLdsCvb;
+  const int n = blockIdx.x / groups, cv0 = (blockIdx.x - n * groups) * kPoolLdsCvb;
+  const int cvb = min(kPoolLdsCvb, CV - cv0);
+  const int HW = H * W;
+  const int items = HW * kPoolLdsCvb;
+  uint4* const xs = reinterpret_cast<uint4*>(pool_smem);
+  uint4* const rvs = xs + items;
+  uint2* const rks = reinterpret_cast<uint2*>(rvs + items);
+  h16_t* const bn = buf + (int64_t)n * HW * ld + cv0 * 8;            // slice 0 of image n at the block's channels
+  uint8_t* const in = idx + (int64_t)n * HW * c + cv0 * 8;           // idx[0] likewise; idx[j] adds j * N*H*W*c
+  pool_lds_stage<kPoolLdsCvb>(xs, bn, ld, items, cvb);
+  __syncthreads();
+#pragma unroll 1
+  for (int j = 0; j < 3; ++j) {
+    pool_lds_row_pass<K, kPoolLdsCvb>(xs, rvs, rks, items, cvb, W);
+    __syncthreads();
+    pool_lds_col_pass<K, kPoolLdsCvb, true>(rvs, rks, xs, items, cvb, H, W, bn + (j + 1) * c, ld, in + (int64_t)j * N * HW * c, c);
+    __syncthreads();
+  }
+}
+
 // backward twin: dy and the arg-max bytes of one image x 4 channel vectors in the LDS, a thread per input pixel x channel vector sums the
 // windows that selected it (k * k LDS reads instead of k * k L2 gathers)
+template <int K, int kPoolLdsCvb>
+__device__ __forceinline__ f32x8 pool_lds_bwd_item(const uint4* gs, const uint2* is, const int ih, const int iw, const int cv, const int H,
+                                                   const int W) {
+  constexpr int PAD = K / 2;
+  f32x8 acc;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc.v[j] = 0.f;
+  // window (oh, ow) covers (ih, iw) with tap kh = ih - oh + PAD, kw = iw - ow + PAD; same accumulation order as maxpool_bwd_kernel
+  // (oh ascending, then ow ascending): bit-identical sums
+  const int oh_lo = max(0, ih - PAD), oh_hi = min(H - 1, ih + PAD);
+  const int ow_lo = max(0, iw - PAD), ow_hi = min(W - 1, iw + PAD);
+  for (int oh = oh_lo; oh <= oh_hi; ++oh) {
+    const int kh = ih - oh + PAD;
+    for (int ow = ow_lo; ow <= ow_hi; ++ow) {
+      const unsigned off = (unsigned)(kh * K + (iw - ow + PAD));
+      const int o = (oh * W + ow) * kPoolLdsCvb + cv;
+      const f32x8 g = unpack8(gs[o]);
+      const uint2 iv = is[o];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned b = ((j < 4 ? iv.x : iv.y) >> (8 * (j & 3))) & 0xffu;
+        if (b == off) acc.v[j] += g.v[j];
+      }
+    }
+  }
+  return acc;
+}
+
 template <int K, int kPoolLdsCvb>
 __global__ __launch_bounds__(256) void maxpool_s1_lds_bwd_kernel(const PoolParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
@@ -294,54 +374,86 @@ __global__ __launch_bounds__(256) void maxpool_s1_lds_bwd_kernel(const PoolParam
     }
   }
   __syncthreads();
-  constexpr int PAD = K / 2;
   for (int i = threadIdx.x; i < HW * kPoolLdsCvb; i += 256) {
     const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
     if (cv >= cvb) continue;
     const int ih = pix / p.W, iw = pix - ih * p.W;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    // window (oh, ow) covers (ih, iw) with tap kh = ih - oh + PAD, kw = iw - ow + PAD; same accumulation order as maxpool_bwd_kernel
-    // (oh ascending, then ow ascending): bit-identical sums
-    const int oh_lo = max(0, ih - PAD), oh_hi = min(p.H - 1, ih + PAD);
-    const int ow_lo = max(0, iw - PAD), ow_hi = min(p.W - 1, iw + PAD);
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-      const int kh = ih - oh + PAD;
-      for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-        const unsigned off = (unsigned)(kh * K + (iw - ow + PAD));
-        const int o = (oh * p.W + ow) * kPoolLdsCvb + cv;
-        const f32x8 g = unpack8(gs[o]);
-        const uint2 iv = is[o];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned b = ((j < 4 ? iv.x : iv.y) >> (8 * (j & 3))) & 0xffu;
-          if (b == off) acc[j] += g.v[j];
-        }
-      }
-    }
+    const f32x8 acc = pool_lds_bwd_item<K, kPoolLdsCvb>(gs, is, ih, iw, cv, p.H, p.W);
     h16_t* const dst = p.dx + ((int64_t)n * HW + pix) * p.ld_dx + (cv0 + cv) * 8;
     f32x8 o;
     if (p.accumulate) {
       const f32x8 old = unpack8(*reinterpret_cast<const uint4*>(dst));
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o.v[j] = old.v[j] + acc[j];
+      for (int j = 0; j < 8; ++j) o.v[j] = old.v[j] + acc.v[j];
     } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
+      for (int j = 0; j < 8; ++j) o.v[j] = acc.v[j];
     }
     *reinterpret_cast<uint4*>(dst) = pack8(o);
   }
 }
 
-static bool pool_lds_ok(const PoolParams& p, bool bwd) {
-  auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+// Backward of the SPPF chain in ONE launch, the in-place three-launch walk (slice j += bwd(slice j + 1), j = 2, 1, 0) kept in the LDS:
+// the block stages slice 3 of the incoming gradient and idx[2]; stage j sums the windows as maxpool_s1_lds_bwd_kernel does, adds the
+// incoming slice j in fp32 and rounds to the 16-bit storage type — exactly the value the in-place walk stores and reads back — into the
+// other LDS buffer, the next stage's input. Only slice 0 goes back to memory: slices 1 and 2 of `d` keep their incoming values (the
+// three-launch walk overwrote them with sums nothing reads). LDS per item: two value buffers + the arg-max bytes (40 bytes).
+template <int K, int kPoolLdsCvb>
+__global__ __launch_bounds__(256) void sppf_chain_bwd_kernel(h16_t* __restrict__ d, const int ld, const uint8_t* __restrict__ idx, const int N,
+                                                             const int c, const int H, const int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
+  const int CV = c >> 3;
+  const int groups = (CV + kPoolLdsCvb - 1) / kPoolLdsCvb;
+  const int n = blockIdx.x / groups, cv0 = (blockIdx.x - n * groups) * kPoolLdsCvb;
+  const int cvb = min(kPoolLdsCvb, CV - cv0);
+  const int HW = H * W;
+  const int items = HW * kPoolLdsCvb;
+  uint4* ga = reinterpret_cast<uint4*>(pool_smem);     // [H*W][CVB] gradient of the stage's OUTPUT slice
+  uint4* gb = ga + items;                              // ... of its input slice, once the stage has run
+  uint2* const is = reinterpret_cast<uint2*>(gb + items);
+  h16_t* const dn = d + (int64_t)n * HW * ld + cv0 * 8;
+  const uint8_t* const in = idx + (int64_t)n * HW * c + cv0 * 8;
+  pool_lds_stage<kPoolLdsCvb>(ga, dn + 3 * c, ld, items, cvb);
+#pragma unroll 1
+  for (int j = 2; j >= 0; --j) {
+    const uint8_t* const ij = in + (int64_t)j * N * HW * c;
+    for (int i = threadIdx.x; i < items; i += 256) {
+      const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
+      if (cv < cvb) is[i] = *reinterpret_cast<const uint2*>(ij + (int64_t)pix * c + cv * 8);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < items; i += 256) {
+      const int pix = i / kPoolLdsCvb, cv = i - pix * kPoolLdsCvb;
+      if (cv >= cvb) continue;
+      h16_t* const dst = dn + (int64_t)pix * ld + j * c + cv * 8;
+      const f32x8 old = unpack8(*reinterpret_cast<const uint4*>(dst));
+      const int ih = pix / W, iw = pix - ih * W;
+      const f32x8 acc = pool_lds_bwd_item<K, kPoolLdsCvb>(ga, is, ih, iw, cv, H, W);
+      f32x8 o;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o.v[q] = old.v[q] + acc.v[q];
+      if (j == 0) *reinterpret_cast<uint4*>(dst) = pack8(o);
+      else gb[i] = pack8(o);
+    }
+    __syncthreads();   // every read of ga / is done: the next stage reloads `is` and reads gb
+    uint4* const t = ga;
+    ga = gb;
+    gb = t;
+  }
+}
+
+static bool pool_lds_enabled() {
   static int on = -1;
   if (on < 0) {
     const char* e = getenv("CVHIP_POOL_LDS");  // 0: the gather kernels for every shape (A/B switch)
     on = (e && e[0] == '0') ? 0 : 1;
   }
-  if (!on || p.s != 1 || !(p.k & 1) || p.pad != p.k / 2 || p.OH != p.H || p.OW != p.W || (p.k != 3 && p.k != 5 && p.k != 9 && p.k != 13)) return false;
+  return on != 0;
+}
+
+static bool pool_lds_ok(const PoolParams& p, bool bwd) {
+  auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+  if (!pool_lds_enabled() || p.s != 1 || !(p.k & 1) || p.pad != p.k / 2 || p.OH != p.H || p.OW != p.W || (p.k != 3 && p.k != 5 && p.k != 9 && p.k != 13)) return false;
   const int cvb = pool_lds_cvb(p.H * p.W, bwd);
   if ((p.C & 7) || p.H * p.W > kPoolLdsMaxPix || cvb == 0 || (int64_t)p.N * ((p.C / 8 + cvb - 1) / cvb) < 128) return false;
   if (bwd) return (p.ld_dy & 7) == 0 && (p.ld_dx & 7) == 0 && a16(p.dy) && a16(p.dx) && ((((uintptr_t)p.cidx) & 7) == 0);
@@ -388,6 +500,48 @@ static int try_pool_lds(const PoolParams& p, bool bwd, hipStream_t s) {
     default: CVHIP_POOL_K(13)
   }
 #undef CVHIP_POOL_K
+}
+
+// channel vectors per block of the SPPF chain kernels (40 bytes of LDS per item in both directions): the widest block of which TWO fit a
+// CU, else the widest that fits at all; 0 = the shape takes the three single-pool launches
+static int sppf_chain_cvb(const void* buf, int ld, const void* idx, int c, int H, int W, int k) {
+  if (!pool_lds_enabled() || k != 5 || (c & 7) || (ld & 7) || ld < 4 * c || (((uintptr_t)buf) & 15) || (((uintptr_t)idx) & 7)) return 0;
+  const int64_t HW = (int64_t)H * W;
+  if (HW > kPoolLdsMaxPix) return 0;
+  for (int cap = 80 * 1024; cap <= 160 * 1024; cap *= 2)
+    for (int cvb = kPoolLdsCvbMax; cvb >= 1; cvb >>= 1)
+      if (HW * cvb * 40 <= cap) return cvb;
+  return 0;
+}
+
+template <int CVB>
+static int launch_sppf_chain(bool bwd, void* buf, int ld, uint8_t* idx, int N, int c, int H, int W, hipStream_t s) {
+  const int groups = (c / 8 + CVB - 1) / CVB;
+  const int lds = H * W * CVB * 40;
+  auto kf = sppf_chain_fwd_kernel<5, CVB>;
+  auto kb = sppf_chain_bwd_kernel<5, CVB>;
+  static bool attr_done[2][64] = {};
+  int devid = 0;
+  (void)hipGetDevice(&devid);
+  bool& done = attr_done[bwd ? 1 : 0][devid & 63];
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(bwd ? reinterpret_cast<const void*>(kb) : reinterpret_cast<const void*>(kf),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+      set_last_error("hipFuncSetAttribute(sppf_chain)", e);
+      return CVHIP_ERR_LAUNCH;
+    }
+    done = true;
+  }
+  if (bwd) hipLaunchKernelGGL(kb, dim3(N * groups), dim3(256), lds, s, (h16_t*)buf, ld, (const uint8_t*)idx, N, c, H, W);
+  else hipLaunchKernelGGL(kf, dim3(N * groups), dim3(256), lds, s, (h16_t*)buf, ld, idx, N, c, H, W);
+  return check_launch(bwd ? "sppf_chain_bwd_kernel" : "sppf_chain_fwd_kernel");
+}
+
+static int sppf_chain_args_ok(const void* buf, int32_t ld, const void* idx, int32_t N, int32_t c, int32_t H, int32_t W, int32_t k) {
+  if (!buf || !idx || N <= 0 || c <= 0 || H <= 0 || W <= 0 || k <= 0 || !(k & 1) || ld < 4 * c) return CVHIP_ERR_INVALID;
+  if (k * k > 255 || (int64_t)N * H * W * c >= (1ll << 31)) return CVHIP_ERR_UNSUPPORTED;
+  return CVHIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1103,6 +1257,35 @@ int cvhip_maxpool2d_bwd(const void* dy, int32_t ld_dy, const uint8_t* argmax, vo
   const int64_t total = (int64_t)N * H * W * ((C + 7) / 8);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("maxpool_bwd_kernel");
+}
+
+int cvhip_sppf_chain_fwd(void* buf, int32_t ld, uint8_t* argmax3, int32_t N, int32_t c, int32_t H, int32_t W, int32_t k, void* stream) {
+  int rc = sppf_chain_args_ok(buf, ld, argmax3, N, c, H, W, k);
+  if (rc != CVHIP_OK) return rc;
+  const int cvb = sppf_chain_cvb(buf, ld, argmax3, c, H, W, k);
+  if (cvb == 4) return launch_sppf_chain<4>(false, buf, ld, argmax3, N, c, H, W, (hipStream_t)stream);
+  if (cvb == 2) return launch_sppf_chain<2>(false, buf, ld, argmax3, N, c, H, W, (hipStream_t)stream);
+  if (cvb == 1) return launch_sppf_chain<1>(false, buf, ld, argmax3, N, c, H, W, (hipStream_t)stream);
+  h16_t* const b = (h16_t*)buf;
+  const int64_t plane = (int64_t)N * H * W * c;
+  for (int j = 0; j < 3 && rc == CVHIP_OK; ++j)
+    rc = cvhip_maxpool2d_fwd(b + j * c, ld, b + (j + 1) * c, ld, argmax3 + j * plane, N, c, H, W, k, 1, k / 2, stream);
+  return rc;
+}
+
+int cvhip_sppf_chain_bwd(void* d, int32_t ld, const uint8_t* argmax3, int32_t N, int32_t c, int32_t H, int32_t W, int32_t k, void* stream) {
+  int rc = sppf_chain_args_ok(d, ld, argmax3, N, c, H, W, k);
+  if (rc != CVHIP_OK) return rc;
+  const int cvb = sppf_chain_cvb(d, ld, argmax3, c, H, W, k);
+  uint8_t* const ix = const_cast<uint8_t*>(argmax3);
+  if (cvb == 4) return launch_sppf_chain<4>(true, d, ld, ix, N, c, H, W, (hipStream_t)stream);
+  if (cvb == 2) return launch_sppf_chain<2>(true, d, ld, ix, N, c, H, W, (hipStream_t)stream);
+  if (cvb == 1) return launch_sppf_chain<1>(true, d, ld, ix, N, c, H, W, (hipStream_t)stream);
+  h16_t* const b = (h16_t*)d;
+  const int64_t plane = (int64_t)N * H * W * c;
+  for (int j = 2; j >= 0 && rc == CVHIP_OK; --j)
+    rc = cvhip_maxpool2d_bwd(b + (j + 1) * c, ld, argmax3 + j * plane, b + j * c, ld, N, c, H, W, k, 1, k / 2, 1, stream);
+  return rc;
 }
 
 int cvhip_upsample2x_cat_fwd(const void* a, int32_t ld_a, int32_t Ca, const void* b, int32_t ld_b, int32_t Cb,

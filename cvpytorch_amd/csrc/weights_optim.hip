@@ -597,7 +597,67 @@ __global__ void i64_add_kernel(long long* v, int64_t n, long long delta) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) v[i] += delta;
 }
+// What follows the fused optimizer in a train step, as ONE launch instead of four (ema_kernel, i64_add_kernel, two zero_fill_kernel):
+// blocks [0, fill_blocks) clear two ranges (the gradient arena, the BatchNorm statistic accumulators), the remaining blocks run the EMA
+// of the floating-point buffers and the step counters' add. The pieces touch disjoint memory; the EMA expression is ema_kernel's.
+struct StepTailParams {
+  float* ema;
+  const float* src;
+  int64_t n_ema;
+  const float* dyn;
+  float decay;
+  long long* cnt;
+  int64_t n_cnt;
+  long long delta;
+  void *za, *zb;
+  int64_t na, nb;  // units of the two ranges: 16 bytes (vec) or 4
+  int vec, fill_blocks;
+};
+__global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
+  if ((int)blockIdx.x < p.fill_blocks) {
+    const int64_t n = p.na + p.nb;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)p.fill_blocks * 256) {
+      if (p.vec) *(i < p.na ? (uint4*)p.za + i : (uint4*)p.zb + (i - p.na)) = make_uint4(0u, 0u, 0u, 0u);
+      else *(i < p.na ? (uint32_t*)p.za + i : (uint32_t*)p.zb + (i - p.na)) = 0u;
+    }
+    return;
+  }
+  const int64_t b = (int64_t)blockIdx.x - p.fill_blocks, nb = (int64_t)gridDim.x - p.fill_blocks;
+  const float decay = p.dyn ? p.dyn[0] : p.decay;
+  for (int64_t i = b * 256 + threadIdx.x; i < p.n_ema + p.n_cnt; i += nb * 256) {
+    if (i < p.n_ema) p.ema[i] = decay * p.ema[i] + (1.f - decay) * p.src[i];
+    else p.cnt[i - p.n_ema] += p.delta;
+  }
+}
 }  // namespace cvhip
+}
+
+int cvhip_train_step_tail(float* ema, const float* src, int64_t n_ema, float decay, const float* dyn_decay, int64_t* counters,
+                          int64_t n_counters, int64_t delta, void* zero_a, int64_t bytes_a, void* zero_b, int64_t bytes_b, void* stream) {
+  if (n_ema < 0 || n_counters < 0 || bytes_a < 0 || bytes_b < 0 || (n_ema > 0 && (!ema || !src)) || (n_counters > 0 && !counters) ||
+      (bytes_a > 0 && !zero_a) || (bytes_b > 0 && !zero_b))
+    return CVHIP_ERR_INVALID;
+  if (((((uintptr_t)zero_a) | ((uintptr_t)zero_b) | (uintptr_t)bytes_a | (uintptr_t)bytes_b) & 3) != 0) return CVHIP_ERR_INVALID;
+  StepTailParams p;
+  p.ema = ema;
+  p.src = src;
+  p.n_ema = n_ema;
+  p.dyn = dyn_decay;
+  p.decay = decay;
+  p.cnt = (long long*)counters;
+  p.n_cnt = n_counters;
+  p.delta = (long long)delta;
+  p.za = zero_a;
+  p.zb = zero_b;
+  p.vec = ((((uintptr_t)zero_a) | ((uintptr_t)zero_b) | (uintptr_t)bytes_a | (uintptr_t)bytes_b) & 15) == 0;
+  p.na = bytes_a / (p.vec ? 16 : 4);
+  p.nb = bytes_b / (p.vec ? 16 : 4);
+  const int64_t fb = cdiv64(p.na + p.nb, 256);
+  p.fill_blocks = (int)(fb < 4096 ? fb : 4096);
+  const int rest = (n_ema + n_counters) > 0 ? grid1d(n_ema + n_counters) : 0;
+  if (p.fill_blocks + rest == 0) return CVHIP_OK;
+  hipLaunchKernelGGL(step_tail_kernel, dim3(p.fill_blocks + rest), dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch("step_tail_kernel");
 }
 
 int cvhip_i64_add(int64_t* v, int64_t n, int64_t delta, void* stream) {

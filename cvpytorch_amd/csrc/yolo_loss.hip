@@ -72,9 +72,12 @@ __device__ __forceinline__ D4 ciou_xywh(float x, float y, float w, float h, floa
 }
 
 // ---- stage A: one wave per candidate ------------------------------------------------------------------
-__global__ __launch_bounds__(256) void yolo_cand_kernel(const YoloLossParams p) {
+// Every stage below is a device function of (level parameters, block index inside the level's grid, blocks of that grid): the per-level
+// kernels pass blockIdx.x / gridDim.x, the multi-level kernels (end of the file) the block's position inside its level's share of a
+// concatenated grid — the same instructions on the same operands either way.
+__device__ __forceinline__ void yolo_cand_body(const YoloLossParams& p, const int bid) {
   const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int c = bid * 4 + (threadIdx.x >> 6);
   if (c >= p.ncand) return;
   const int T = p.T, A = p.A;
   const int off = c / (A * T);
@@ -154,6 +157,8 @@ __global__ __launch_bounds__(256) void yolo_cand_kernel(const YoloLossParams p) 
   if (lane == 0) cs[2] = p.nc > 1 ? lsum : 0.f;
 }
 
+__global__ __launch_bounds__(256) void yolo_cand_kernel(const YoloLossParams p) { yolo_cand_body(p, (int)blockIdx.x); }
+
 // ---- deterministic single-block reductions --------------------------------------------------------------
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
   const int t = threadIdx.x;
@@ -216,12 +221,12 @@ __device__ __forceinline__ void yolo_cand_reduce(const YoloLossParams& p, float*
 // IT: index type of the flat walks below — unsigned 32-bit whenever the element count allows (the 64-bit divisions by run-time values
 // cost ~100 instructions each; every launch of the benchmarked configurations takes the 32-bit instance)
 template <typename IT>
-__global__ __launch_bounds__(256) void yolo_obj_bwd_fill_kernel(const YoloLossParams p) {
+__device__ __forceinline__ void yolo_obj_bwd_fill_body(const YoloLossParams& p, const int bid, const int nblk) {
   const IT VP = (IT)(p.ld >> 3);  // 16-byte vectors per pixel
   const IT HW = (IT)p.H * (IT)p.W;
   const IT nvec = (IT)p.N * HW * VP;
   const float go = (p.gout ? p.gout[0] : 1.f) * p.k_obj;
-  const IT step = (IT)gridDim.x * 256;
+  const IT step = (IT)nblk * 256;
   // the vector's position inside its pixel is thread-invariant when VP is a power of two dividing the grid stride (ld = 256: VP = 32):
   // which anchors' objectness channels fall into it is then decided once, and only those lanes (3 of 32) do any index arithmetic
   const bool inv = (VP & (VP - 1)) == 0 && (step & (VP - 1)) == 0;
@@ -234,8 +239,8 @@ __global__ __launch_bounds__(256) void yolo_obj_bwd_fill_kernel(const YoloLossPa
     }
     return m;
   };
-  const unsigned my_mask = inv ? anchors_of((int)(((IT)blockIdx.x * 256 + threadIdx.x) & (VP - 1)) * 8) : 0u;
-  for (IT i = (IT)blockIdx.x * 256 + threadIdx.x; i < nvec; i += step) {
+  const unsigned my_mask = inv ? anchors_of((int)(((IT)bid * 256 + threadIdx.x) & (VP - 1)) * 8) : 0u;
+  for (IT i = (IT)bid * 256 + threadIdx.x; i < nvec; i += step) {
     IT pix;
     int c0;
     unsigned mask;
@@ -267,14 +272,18 @@ __global__ __launch_bounds__(256) void yolo_obj_bwd_fill_kernel(const YoloLossPa
   }
 }
 
+template <typename IT>
+__global__ __launch_bounds__(256) void yolo_obj_bwd_fill_kernel(const YoloLossParams p) {
+  yolo_obj_bwd_fill_body<IT>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // ---- stage B: objectness over every cell ------------------------------------------------------------------
 template <bool BWD, typename IT>
-__global__ __launch_bounds__(256) void yolo_obj_kernel(const YoloLossParams p) {
-  __shared__ float red[256];
+__device__ __forceinline__ void yolo_obj_body(const YoloLossParams& p, const int bid, const int nblk, float* red) {
   const IT ncell = (IT)p.N * (IT)p.A * (IT)p.H * (IT)p.W;
   const float go = BWD ? (p.gout ? p.gout[0] : 1.f) * p.k_obj : 0.f;
   float acc = 0.f;
-  for (IT i = (IT)blockIdx.x * 256 + threadIdx.x; i < ncell; i += (IT)gridDim.x * 256) {
+  for (IT i = (IT)bid * 256 + threadIdx.x; i < ncell; i += (IT)nblk * 256) {
     // cell order (n, a, gj, gi); memory order pixel-major: walk pixels so neighbouring lanes touch neighbouring rows
     IT r = i / (IT)p.W;
     const int gi = (int)(i - r * (IT)p.W);
@@ -299,13 +308,19 @@ __global__ __launch_bounds__(256) void yolo_obj_kernel(const YoloLossParams p) {
       if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
       __syncthreads();
     }
-    if (threadIdx.x == 0) p.partial[blockIdx.x] = red[0];
+    if (threadIdx.x == 0) p.partial[bid] = red[0];
   }
 }
 
-__global__ __launch_bounds__(1024) void yolo_obj_reduce_kernel(const YoloLossParams p, int nblocks) {
-  __shared__ float red[1024];
-  if (blockIdx.x == 1) {
+template <bool BWD, typename IT>
+__global__ __launch_bounds__(256) void yolo_obj_kernel(const YoloLossParams p) {
+  __shared__ float red[256];
+  yolo_obj_body<BWD, IT>(p, (int)blockIdx.x, (int)gridDim.x, red);
+}
+
+// block 0 of a level: objectness partials, block 1: candidate sums
+__device__ __forceinline__ void yolo_obj_reduce_body(const YoloLossParams& p, const int nblocks, const int bid, float* red) {
+  if (bid == 1) {
     yolo_cand_reduce(p, red);
     return;
   }
@@ -315,10 +330,15 @@ __global__ __launch_bounds__(1024) void yolo_obj_reduce_kernel(const YoloLossPar
   if (threadIdx.x == 0) p.sums[3] = v;
 }
 
+__global__ __launch_bounds__(1024) void yolo_obj_reduce_kernel(const YoloLossParams p, int nblocks) {
+  __shared__ float red[1024];
+  yolo_obj_reduce_body(p, nblocks, (int)blockIdx.x, red);
+}
+
 // ---- stage C (backward): per cell, the winner candidate sums the box/class gradients of all its duplicates -------
-__global__ __launch_bounds__(256) void yolo_cand_bwd_kernel(const YoloLossParams p) {
+__device__ __forceinline__ void yolo_cand_bwd_body(const YoloLossParams& p, const int bid) {
   const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int c = bid * 4 + (threadIdx.x >> 6);
   if (c >= p.ncand) return;
   const int cell = p.cell[c];
   if (cell < 0 || p.winner[cell] != c + 1) return;
@@ -366,6 +386,8 @@ __global__ __launch_bounds__(256) void yolo_cand_bwd_kernel(const YoloLossParams
   if (ch1 < p.NO) dst[ch1] = (h16_t)(acc1 * kc);
 }
 
+__global__ __launch_bounds__(256) void yolo_cand_bwd_kernel(const YoloLossParams p) { yolo_cand_bwd_body(p, (int)blockIdx.x); }
+
 // ---- stage D (backward, round 6): column sums of the head gradient from the loss's own compact state -------------------------------
 // The detect convolutions carry a bias (yolov5_head.py: nn.Conv2d(ch, na * no, 1)): its gradient is the column sum of the gradient
 // map, which the engine used to compute by reading the whole map again (275 MB per YOLOv5-s step, 3 x 52 us) — although the map is
@@ -375,16 +397,15 @@ __global__ __launch_bounds__(256) void yolo_cand_bwd_kernel(const YoloLossParams
 // deterministic. The sums are those of the fp32 values BEFORE their rounding into the 16-bit map.
 constexpr int kBiasRows = CVHIP_YOLO_BIAS_ROWS;
 template <typename IT>
-__global__ __launch_bounds__(256) void yolo_bias_partial_kernel(const YoloLossParams p, float* __restrict__ part) {
-  __shared__ float wacc[4][kLossMaxA * 128];
-  __shared__ float ored[kLossMaxA][256];
+__device__ __forceinline__ void yolo_bias_partial_body(const YoloLossParams& p, float* __restrict__ part, const int bid, const int nblk,
+                                                       float (*wacc)[kLossMaxA * 128], float (*ored)[256]) {
   const int K = p.A * p.NO;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   for (int i = t; i < 4 * kLossMaxA * 128; i += 256) (&wacc[0][0])[i] = 0.f;
   __syncthreads();
   // candidates: a contiguous slice per block, groups of 64 dealt to the waves in order; a lane owns channels lane, lane + 64
-  const int per_blk = (p.ncand + gridDim.x - 1) / gridDim.x;
-  const int c_begin = blockIdx.x * per_blk, c_end = min(c_begin + per_blk, p.ncand);
+  const int per_blk = (p.ncand + nblk - 1) / nblk;
+  const int c_begin = bid * per_blk, c_end = min(c_begin + per_blk, p.ncand);
   for (int g0 = c_begin + wave * 64; g0 < c_end; g0 += 256) {
     const int c = g0 + lane;
     unsigned long long m = __ballot(c < c_end && p.cell[c] >= 0);
@@ -423,8 +444,8 @@ __global__ __launch_bounds__(256) void yolo_bias_partial_kernel(const YoloLossPa
   for (int k = 0; k < kLossMaxA; ++k) oa[k] = 0.f;
   {
     const IT ncell = (IT)p.N * (IT)p.A * (IT)p.H * (IT)p.W, HW = (IT)p.H * (IT)p.W;
-    const IT per = (ncell + gridDim.x - 1) / gridDim.x;
-    const IT i_begin = (IT)blockIdx.x * per;
+    const IT per = (ncell + (unsigned)nblk - 1) / (unsigned)nblk;
+    const IT i_begin = (IT)bid * per;
     IT i_end = i_begin + per;
     if (i_end > ncell) i_end = ncell;
     for (IT i0 = i_begin + t; i0 < i_end; i0 += 256 * 8) {  // 8 independent loads in flight per lane (64 blocks walk 1.2 M cells)
@@ -456,12 +477,19 @@ __global__ __launch_bounds__(256) void yolo_bias_partial_kernel(const YoloLossPa
   const float n = p.sums[0];
   const float g = p.gout ? p.gout[0] : 1.f;
   const float kb = n > 0.f ? g * p.k_box / n : 0.f, kc = n > 0.f ? g * p.k_cls / n : 0.f, go = g * p.k_obj;
-  float* const row = part + (int64_t)blockIdx.x * 2 * K;
+  float* const row = part + (int64_t)bid * 2 * K;
   for (int ch = t; ch < K; ch += 256) {
     const int a = ch / p.NO, o = ch - a * p.NO;
     const float v = ((wacc[0][ch] + wacc[1][ch]) + wacc[2][ch]) + wacc[3][ch];
     row[ch] = o == 4 ? ored[a][0] * go : v * (o < 4 ? kb : kc);
   }
+}
+
+template <typename IT>
+__global__ __launch_bounds__(256) void yolo_bias_partial_kernel(const YoloLossParams p, float* __restrict__ part) {
+  __shared__ float wacc[4][kLossMaxA * 128];
+  __shared__ float ored[kLossMaxA][256];
+  yolo_bias_partial_body<IT>(p, part, (int)blockIdx.x, (int)gridDim.x, wacc, ored);
 }
 
 // ---- final scalars ----------------------------------------------------------------------------------------
@@ -486,7 +514,68 @@ __global__ void yolo_finalize_kernel(const float* sums, int L, const float* ncel
   stats[2] = lcls;
 }
 
-static int fill(YoloLossParams& p, const cvhip_yolo_loss_desc* d, const void* raw, const float* targets, void* ws, float* sums) {
+// ---- all levels in one launch per stage ---------------------------------------------------------------------------------------------
+// The grid of a stage is the concatenation of the levels' own grids: block b belongs to the level l with first[l] <= b < first[l + 1]
+// and runs that level's stage as block b - first[l] of first[l + 1] - first[l]. The table travels by value in the kernel arguments
+// (about 1 KB with four levels; nothing is copied to the device at call time, so the sequence stays capturable).
+constexpr int kLossMaxLevels = CVHIP_YOLO_MAX_LEVELS;
+struct YoloLevelsParams {
+  YoloLossParams lv[kLossMaxLevels];
+  int first[kLossMaxLevels + 1];  // prefix sums of the levels' block counts in THIS launch
+  int nb_obj[kLossMaxLevels];     // reduce stage: blocks the level's objectness pass ran with
+  float* part[kLossMaxLevels];    // bias stage: the level's partial rows
+  int L;
+};
+
+__device__ __forceinline__ int level_of_block(const YoloLevelsParams& P, const int b) {
+  int l = 0;
+  while (l + 1 < P.L && b >= P.first[l + 1]) ++l;
+  return l;
+}
+
+__global__ __launch_bounds__(256) void yolo_cand_levels_kernel(const YoloLevelsParams P) {
+  const int l = level_of_block(P, (int)blockIdx.x);
+  yolo_cand_body(P.lv[l], (int)blockIdx.x - P.first[l]);
+}
+
+__global__ __launch_bounds__(256) void yolo_obj_levels_kernel(const YoloLevelsParams P) {
+  __shared__ float red[256];
+  const int l = level_of_block(P, (int)blockIdx.x);
+  yolo_obj_body<false, unsigned>(P.lv[l], (int)blockIdx.x - P.first[l], P.first[l + 1] - P.first[l], red);
+}
+
+__global__ __launch_bounds__(1024) void yolo_obj_reduce_levels_kernel(const YoloLevelsParams P) {
+  __shared__ float red[1024];
+  const int l = (int)blockIdx.x >> 1;
+  yolo_obj_reduce_body(P.lv[l], P.nb_obj[l], (int)blockIdx.x & 1, red);
+}
+
+__global__ __launch_bounds__(256) void yolo_obj_bwd_fill_levels_kernel(const YoloLevelsParams P) {
+  const int l = level_of_block(P, (int)blockIdx.x);
+  yolo_obj_bwd_fill_body<unsigned>(P.lv[l], (int)blockIdx.x - P.first[l], P.first[l + 1] - P.first[l]);
+}
+
+__global__ __launch_bounds__(256) void yolo_cand_bwd_levels_kernel(const YoloLevelsParams P) {
+  const int l = level_of_block(P, (int)blockIdx.x);
+  yolo_cand_bwd_body(P.lv[l], (int)blockIdx.x - P.first[l]);
+}
+
+__global__ __launch_bounds__(256) void yolo_bias_partial_levels_kernel(const YoloLevelsParams P) {
+  __shared__ float wacc[4][kLossMaxA * 128];
+  __shared__ float ored[kLossMaxA][256];
+  const int l = (int)blockIdx.x / kBiasRows;
+  yolo_bias_partial_body<unsigned>(P.lv[l], P.part[l], (int)blockIdx.x - l * kBiasRows, kBiasRows, wacc, ored);
+}
+
+// the per-level workspace in two pieces: `front` = winner + head (cleared before every forward), `rest` = everything else
+static int64_t ws_front_bytes(int64_t ncell) { return (ncell * 4 + 255) / 256 * 256 * 2; }
+static int64_t ws_rest_bytes(int64_t ncell, int64_t ncand, int64_t gs) {
+  auto r = [](int64_t b) { return (b + 255) / 256 * 256; };
+  return r(ncand * 4) * 2 + r(ncand * kCandStride * 4) + r(ncand * gs * 4) + r(1024 * 4) + r(ncell * 4);
+}
+
+static int fill(YoloLossParams& p, const cvhip_yolo_loss_desc* d, const void* raw, const float* targets, void* ws, float* sums,
+                void* ws_rest = nullptr) {
   if (!d || !raw || !targets || !ws || !sums) return CVHIP_ERR_INVALID;
   if (d->N <= 0 || d->A <= 0 || d->A > kLossMaxA || d->NO < 6 || d->NO > 128 || d->H <= 0 || d->W <= 0 || d->T <= 0 || d->ld < d->A * d->NO)
     return CVHIP_ERR_INVALID;
@@ -517,6 +606,7 @@ static int fill(YoloLossParams& p, const cvhip_yolo_loss_desc* d, const void* ra
   };
   p.winner = (int*)take(ncell * 4);
   p.head = (int*)take(ncell * 4);
+  if (ws_rest) w = (unsigned char*)ws_rest;  // multi-level layout: every level's winner / head first, the other arrays behind them
   p.next = (int*)take(ncand * 4);
   p.cell = (int*)take(ncand * 4);
   p.cand = (float*)take(ncand * kCandStride * 4);
@@ -630,6 +720,123 @@ static int level_bwd(const cvhip_yolo_loss_desc* d, const void* raw, const float
     else hipLaunchKernelGGL(yolo_bias_partial_kernel<int64_t>, dim3(kBiasRows), dim3(256), 0, st, p, bias_partial);
   }
   return check_launch("yolov5_loss_level_bwd");
+}
+
+// ---- all levels at once: one launch per stage (YoloLevelsParams above) ----------------------------------------------------------------
+// Workspace: [winner_0 head_0 winner_1 head_1 ...] then every level's remaining arrays, so ONE fill clears what the forward needs cleared.
+int64_t cvhip_yolov5_loss_workspace_bytes_levels(const cvhip_yolo_loss_desc* d, int32_t levels) {
+  if (!d || levels <= 0 || levels > kLossMaxLevels) return CVHIP_ERR_INVALID;
+  int64_t total = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t b = cvhip_yolov5_loss_workspace_bytes(d + l);  // front + rest of the level: the same arrays, placed differently
+    if (b < 0) return b;
+    total += b;
+  }
+  return total;
+}
+
+static int levels_fill(YoloLevelsParams& P, const cvhip_yolo_loss_desc* d, int levels, const void* const* raws, const float* targets, void* ws,
+                       float* sums, int64_t* front_bytes) {
+  if (!d || !raws || !ws || !sums || levels <= 0 || levels > kLossMaxLevels) return CVHIP_ERR_INVALID;
+  int64_t front = 0;
+  for (int l = 0; l < levels; ++l) front += ws_front_bytes((int64_t)d[l].N * d[l].A * d[l].H * d[l].W);
+  unsigned char* f = (unsigned char*)ws;
+  unsigned char* r = f + front;
+  for (int l = 0; l < levels; ++l) {
+    const int rc = fill(P.lv[l], d + l, raws[l], targets, f, sums + l * 4, r);
+    if (rc != CVHIP_OK) return rc;
+    const int64_t ncell = (int64_t)d[l].N * d[l].A * d[l].H * d[l].W;
+    f += ws_front_bytes(ncell);
+    r += ws_rest_bytes(ncell, P.lv[l].ncand, P.lv[l].gstride);
+  }
+  for (int l = levels; l < kLossMaxLevels; ++l) P.lv[l] = P.lv[0];  // never selected; keeps the argument block defined
+  for (int l = 0; l < kLossMaxLevels; ++l) {
+    P.nb_obj[l] = 0;
+    P.part[l] = nullptr;
+  }
+  P.L = levels;
+  *front_bytes = front;
+  return CVHIP_OK;
+}
+
+int cvhip_yolov5_loss_fwd_levels(const cvhip_yolo_loss_desc* d, int32_t levels, const void* const* raws, const float* targets, void* ws,
+                                 float* sums, void* stream) {
+  YoloLevelsParams P;
+  int64_t front = 0;
+  int rc = levels_fill(P, d, levels, raws, targets, ws, sums, &front);
+  if (rc != CVHIP_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int nb[kLossMaxLevels];
+  for (int l = 0; l < levels; ++l) {
+    const YoloLossParams& p = P.lv[l];
+    const int64_t ncell = (int64_t)p.N * p.A * p.H * p.W;
+    nb[l] = (int)(cdiv64(ncell, 256) < 1024 ? cdiv64(ncell, 256) : 1024);
+    if (ncell + (int64_t)nb[l] * 256 >= (1ll << 32)) return CVHIP_ERR_UNSUPPORTED;  // 64-bit walks: the per-level entries
+  }
+  rc = zero_fill(ws, front, st);
+  if (rc != CVHIP_OK) return rc;
+  P.first[0] = 0;
+  for (int l = 0; l < kLossMaxLevels; ++l) P.first[l + 1] = P.first[l] + (l < levels ? cdiv(P.lv[l].ncand, 4) : 0);
+  hipLaunchKernelGGL(yolo_cand_levels_kernel, dim3(P.first[levels]), dim3(256), 0, st, P);
+  for (int l = 0; l < kLossMaxLevels; ++l) P.first[l + 1] = P.first[l] + (l < levels ? nb[l] : 0);
+  hipLaunchKernelGGL(yolo_obj_levels_kernel, dim3(P.first[levels]), dim3(256), 0, st, P);
+  for (int l = 0; l < levels; ++l) P.nb_obj[l] = nb[l];
+  hipLaunchKernelGGL(yolo_obj_reduce_levels_kernel, dim3(2 * levels), dim3(1024), 0, st, P);
+  return check_launch("yolov5_loss_fwd_levels");
+}
+
+int cvhip_yolov5_loss_bwd_levels(const cvhip_yolo_loss_desc* d, int32_t levels, const void* const* raws, const float* targets, void* ws,
+                                 const float* sums, const float* gout, float k_box, float k_cls, const float* k_obj, void* const* draws,
+                                 float* const* bias_partials, void* stream) {
+  YoloLevelsParams P;
+  int64_t front = 0;
+  int rc = levels_fill(P, d, levels, raws, targets, ws, const_cast<float*>(sums), &front);
+  if (rc != CVHIP_OK) return rc;
+  if (!k_obj || !draws) return CVHIP_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  for (int l = 0; l < levels; ++l) {
+    if (!draws[l] || (bias_partials && !bias_partials[l])) return CVHIP_ERR_INVALID;
+    YoloLossParams& p = P.lv[l];
+    p.draw = (h16_t*)draws[l];
+    p.gout = gout;
+    p.k_box = k_box;
+    p.k_cls = k_cls;
+    p.k_obj = k_obj[l];
+    if (bias_partials) P.part[l] = bias_partials[l];
+  }
+  // objectness channel + zeros: the vector-path levels share one launch, a level whose pitch or address rules that path out is
+  // written by the two-pass form of the per-level entry
+  YoloLevelsParams F = P;
+  int nf = 0;
+  F.first[0] = 0;
+  for (int l = 0; l < levels; ++l) {
+    const YoloLossParams& p = P.lv[l];
+    if ((p.ld & 7) == 0 && (((uintptr_t)p.draw) & 15) == 0) {
+      const int64_t nvec = (int64_t)p.N * p.H * p.W * (p.ld >> 3);
+      const int nbf = (int)(cdiv64(nvec, 256 * 4) < 8192 ? cdiv64(nvec, 256 * 4) : 8192);
+      if (nvec + (int64_t)nbf * 256 >= (1ll << 32)) return CVHIP_ERR_UNSUPPORTED;
+      F.lv[nf] = p;
+      F.first[nf + 1] = F.first[nf] + (nbf > 0 ? nbf : 1);
+      ++nf;
+    } else {
+      const int64_t ncell = (int64_t)p.N * p.A * p.H * p.W;
+      rc = zero_fill(p.draw, (int64_t)p.N * p.H * p.W * p.ld * 2, st);
+      if (rc != CVHIP_OK) return rc;
+      const int nbo = (int)(cdiv64(ncell, 256) < 8192 ? cdiv64(ncell, 256) : 8192);
+      if (ncell + (int64_t)nbo * 256 < (1ll << 32)) hipLaunchKernelGGL((yolo_obj_kernel<true, unsigned>), dim3(nbo), dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((yolo_obj_kernel<true, int64_t>), dim3(nbo), dim3(256), 0, st, p);
+    }
+  }
+  if (nf > 0) {
+    for (int l = nf; l < kLossMaxLevels; ++l) F.first[l + 1] = F.first[l];
+    F.L = nf;
+    hipLaunchKernelGGL(yolo_obj_bwd_fill_levels_kernel, dim3(F.first[nf]), dim3(256), 0, st, F);
+  }
+  P.first[0] = 0;
+  for (int l = 0; l < kLossMaxLevels; ++l) P.first[l + 1] = P.first[l] + (l < levels ? cdiv(P.lv[l].ncand, 4) : 0);
+  hipLaunchKernelGGL(yolo_cand_bwd_levels_kernel, dim3(P.first[levels]), dim3(256), 0, st, P);
+  if (bias_partials) hipLaunchKernelGGL(yolo_bias_partial_levels_kernel, dim3(kBiasRows * levels), dim3(256), 0, st, P);
+  return check_launch("yolov5_loss_bwd_levels");
 }
 
 }  // extern "C"

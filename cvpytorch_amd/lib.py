@@ -24,6 +24,7 @@ RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 DGRAD_CLASS_INTS = 12
 REDUCE_SCRATCH_ROWS = 64  # CVHIP_REDUCE_SCRATCH_ROWS
 YOLO_BIAS_ROWS = 256  # CVHIP_YOLO_BIAS_ROWS
+YOLO_MAX_LEVELS = 4  # CVHIP_YOLO_MAX_LEVELS
 BN_ACC_SHARDS = 16  # CVHIP_BN_ACC_SHARDS
 
 
@@ -160,6 +161,8 @@ SIGNATURES = {
     "cvhip_colsum_finalize": (_i32, [_p, _i32, _i32, _p, _i32, _p]),
     "cvhip_maxpool2d_fwd": (_i32, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     "cvhip_maxpool2d_bwd": (_i32, [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    "cvhip_sppf_chain_fwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p]),
+    "cvhip_sppf_chain_bwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p]),
     "cvhip_upsample2x_cat_fwd": (_i32, [_p, _i32, _i32, _p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _p]),
     "cvhip_upsample2x_bwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p]),
     "cvhip_zero_fill": (_i32, [_p, _i64, _p]),
@@ -210,12 +213,16 @@ SIGNATURES = {
     "cvhip_loss_scale_update": (_i32, [_p, _p, _f32, _f32, _i32, _p]),
     "cvhip_i64_add": (_i32, [_p, _i64, _i64, _p]),
     "cvhip_ema_update": (_i32, [_p, _p, _i64, _f32, _p, _p]),
+    "cvhip_train_step_tail": (_i32, [_p, _p, _i64, _f32, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _p]),
     "cvhip_u8_nhwc_to_bf16_norm": (_i32, [_p, _i64, _i32, _p, _i32, _p, _p, _p]),
     "cvhip_yolov5_loss_workspace_bytes": (_i64, [_ylp]),
     "cvhip_yolov5_loss_level_fwd": (_i32, [_ylp, _p, _p, _p, _p, _p]),
     "cvhip_yolov5_loss_finalize": (_i32, [_p, _i32, _p, _p, _f32, _f32, _f32, _i32, _f32, _p, _p, _p]),
     "cvhip_yolov5_loss_level_bwd": (_i32, [_ylp, _p, _p, _p, _p, _p, _f32, _f32, _f32, _p, _p]),
     "cvhip_yolov5_loss_level_bwd_bias": (_i32, [_ylp, _p, _p, _p, _p, _p, _f32, _f32, _f32, _p, _p, _p]),
+    "cvhip_yolov5_loss_workspace_bytes_levels": (_i64, [_ylp, _i32]),
+    "cvhip_yolov5_loss_fwd_levels": (_i32, [_ylp, _i32, _pp, _p, _p, _p, _p]),
+    "cvhip_yolov5_loss_bwd_levels": (_i32, [_ylp, _i32, _pp, _p, _p, _p, _p, _f32, _f32, C.POINTER(_f32), _pp, _pp, _p]),
     "cvhip_ota_workspace_bytes": (_i64, [_otp]),
     "cvhip_ota_assign": (_i32, [_otp, _pp, _p, _p, _p, _p]),
     "cvhip_ota_read_overflow": (_i32, [_otp, _p, _p, _p]),

@@ -1804,13 +1804,23 @@ class MaxPool2d(torch.autograd.Function):
         return dx, None, None, None
 
 
+def _has_sppf_chain():
+    # only an OLDER build under A/B through CVHIP_LIB can lack the entry (lib.load() insists on every entry otherwise)
+    return hasattr(L.load(), "cvhip_sppf_chain_fwd")
+
+
 class SppfChain(torch.autograd.Function):
     """SPPF's pooling chain + concat (yolo_modules.py:186-194: x, m(x), m(m(x)), m(m(m(x))) concatenated) on ONE buffer.
 
     `x0` is the [:, :c] slice of an (N, 4c, H, W) NHWC buffer that the 1x1 conv in front already wrote (its `out=`); the three stride-1
     pools write their outputs straight into the other three slices — no concat copy. Backward walks the chain on the incoming concat
     gradient IN PLACE: slice j receives the pool gradient of slice j + 1 through cvhip_maxpool2d_bwd's accumulate form, so the three
-    gradient-accumulation adds (ops.Fanout) and their temporaries disappear; the first slice is returned as the gradient of x0."""
+    gradient-accumulation adds (ops.Fanout) and their temporaries disappear; the first slice is returned as the gradient of x0.
+
+    Both directions are ONE launch where the map fits the LDS (cvhip_sppf_chain_fwd / _bwd; the entry points themselves fall back to the
+    three single-pool launches otherwise), with the values, arg-max bytes and slice-0 gradient of the three-launch chain bit for bit.
+    What changed with that: the one-launch backward keeps the intermediate sums in the LDS and writes ONLY slice 0 — slices 1 and 2 of
+    the incoming gradient, which the three-launch walk overwrote with those sums, now keep their incoming values. Nothing reads them."""
 
     @staticmethod
     def forward(ctx, x0, k):
@@ -1821,10 +1831,13 @@ class SppfChain(torch.autograd.Function):
         pad = k // 2
         st = _stream()
         idx = torch.empty((3, N, H, W, c), dtype=torch.uint8, device=x0v.device)
-        esz = x0v.element_size()
-        for j in range(3):
-            L.call("cvhip_maxpool2d_fwd", x0v.data_ptr() + j * c * esz, ld, x0v.data_ptr() + (j + 1) * c * esz, ld, idx[j].data_ptr(),
-                   N, c, H, W, k, 1, pad, st)
+        if _has_sppf_chain():
+            L.call("cvhip_sppf_chain_fwd", x0v.data_ptr(), ld, idx.data_ptr(), N, c, H, W, k, st)
+        else:
+            esz = x0v.element_size()
+            for j in range(3):
+                L.call("cvhip_maxpool2d_fwd", x0v.data_ptr() + j * c * esz, ld, x0v.data_ptr() + (j + 1) * c * esz, ld, idx[j].data_ptr(),
+                       N, c, H, W, k, 1, pad, st)
         ctx.meta = (N, c, H, W, k, pad)
         ctx.save_for_backward(idx)
         return x0v.as_strided((N, 4 * c, H, W), (H * W * 4 * c, 1, W * 4 * c, 4 * c))   # fresh alias of the whole buffer (as ops.Cat does)
@@ -1844,10 +1857,13 @@ class SppfChain(torch.autograd.Function):
             d = d.clone(memory_format=torch.channels_last)
             d, ld = as_nhwc(d)
         st = _stream()
-        esz = d.element_size()
-        for j in (2, 1, 0):   # slice j += maxpool_bwd(slice j + 1)
-            L.call("cvhip_maxpool2d_bwd", d.data_ptr() + (j + 1) * c * esz, ld, idx[j].data_ptr(), d.data_ptr() + j * c * esz, ld,
-                   N, c, H, W, k, 1, pad, 1, st)
+        if _has_sppf_chain():
+            L.call("cvhip_sppf_chain_bwd", d.data_ptr(), ld, idx.data_ptr(), N, c, H, W, k, st)
+        else:
+            esz = d.element_size()
+            for j in (2, 1, 0):   # slice j += maxpool_bwd(slice j + 1)
+                L.call("cvhip_maxpool2d_bwd", d.data_ptr() + (j + 1) * c * esz, ld, idx[j].data_ptr(), d.data_ptr() + j * c * esz, ld,
+                       N, c, H, W, k, 1, pad, 1, st)
         return d[:, :c], None
 
 
@@ -2610,13 +2626,24 @@ class YoloV5LossFused(torch.autograd.Function):
             L.call("cvhip_ota_assign", C.byref(od), ptrs, tg.data_ptr(), ota_ws.data_ptr(), assign.data_ptr(), st)
             ctx.ota_keep = (ota_ws, od)
             cfg.last_assign = assign   # diagnostics / tests
+        # without an external assignment all levels go through the multi-level entries: one launch per stage for the whole pyramid and
+        # one workspace (cvhip_yolov5_loss_fwd_levels); the OTA path keeps the per-level calls
+        # (hasattr: only an OLDER build under A/B through CVHIP_LIB can lack them — lib.load() insists on every entry otherwise)
+        multi = assign is None and nl <= L.YOLO_MAX_LEVELS and hasattr(L.load(), "cvhip_yolov5_loss_fwd_levels")
+        darr = (L.YoloLossDesc * nl)()
         for i, (r, ld) in enumerate(raws):
             N, Cc, H, W = r.shape
             if Cc != A * NO:
                 raise L.CvhipError("yolov5 loss: head map has %d channels, expected %d" % (Cc, A * NO))
-            d = L.YoloLossDesc(N, A, NO, H, W, ld, T, float(cfg.anchor_t))
+            d = darr[i]
+            d.N, d.A, d.NO, d.H, d.W, d.ld, d.T, d.anchor_t = N, A, NO, H, W, ld, T, float(cfg.anchor_t)
             for j, v in enumerate([float(x) for pair in cfg.anchors[i] for x in pair]):
                 d.anchors[j] = v
+            descs.append(d)
+            maps.append(r)
+            ncells.append(float(N * A * H * W))
+            if multi:
+                continue
             nbytes = L.load().cvhip_yolov5_loss_workspace_bytes(C.byref(d))
             if nbytes < 0:
                 L.check(int(nbytes), "cvhip_yolov5_loss_workspace_bytes")
@@ -2626,10 +2653,15 @@ class YoloV5LossFused(torch.autograd.Function):
                        sums[i].data_ptr(), st)
             else:
                 L.call("cvhip_yolov5_loss_level_fwd", C.byref(d), r.data_ptr(), tg.data_ptr(), ws.data_ptr(), sums[i].data_ptr(), st)
-            descs.append(d)
             wss.append(ws)
-            maps.append(r)
-            ncells.append(float(N * A * H * W))
+        if multi:
+            nbytes = L.load().cvhip_yolov5_loss_workspace_bytes_levels(darr, nl)
+            if nbytes < 0:
+                L.check(int(nbytes), "cvhip_yolov5_loss_workspace_bytes_levels")
+            wss.append(torch.empty((int(nbytes),), dtype=torch.uint8, device=dev))
+            ptrs = (C.c_void_p * nl)(*[r.data_ptr() for r in maps])
+            L.call("cvhip_yolov5_loss_fwd_levels", darr, nl, ptrs, tg.data_ptr(), wss[0].data_ptr(), sums.data_ptr(), st)
+        ctx.multi, ctx.darr = multi, darr
         key = (tuple(ncells), tuple(cfg.balance[:nl]), str(dev))
         consts = cfg._const_cache.get(key)
         if consts is None:  # built once per shape/device (a host->device copy here would break hipGraph capture)
@@ -2657,14 +2689,27 @@ class YoloV5LossFused(torch.autograd.Function):
         outs = []
         nc = cfg.num_classes
         clear_colsums()
+        k_box, k_cls = float(cfg.hyp_box) * ctx.bs, (float(cfg.hyp_cls) * ctx.bs / nc) if nc > 1 else 0.0
+        k_obj = [float(cfg.hyp_obj) * float(cfg.balance[i]) * ctx.bs / ctx.ncells[i] for i in range(len(maps))]
+        draws, bps = [], []
         for i, r in enumerate(maps):
             d = ctx.descs[i]
             draw = torch.empty((d.N, d.H, d.W, d.ld), dtype=ACT_DTYPE, device=r.device)
             K = d.A * d.NO
             bp = torch.empty((L.YOLO_BIAS_ROWS + L.REDUCE_SCRATCH_ROWS, 2, K), dtype=torch.float32, device=r.device)
-            L.call("cvhip_yolov5_loss_level_bwd_bias", C.byref(d), r.data_ptr(), tg.data_ptr(), ctx.wss[i].data_ptr(), sums[i].data_ptr(),
-                   g.data_ptr(), float(cfg.hyp_box) * ctx.bs, (float(cfg.hyp_cls) * ctx.bs / nc) if nc > 1 else 0.0,
-                   float(cfg.hyp_obj) * float(cfg.balance[i]) * ctx.bs / ctx.ncells[i], draw.data_ptr(), bp.data_ptr(), st)
+            if not ctx.multi:
+                L.call("cvhip_yolov5_loss_level_bwd_bias", C.byref(d), r.data_ptr(), tg.data_ptr(), ctx.wss[i].data_ptr(), sums[i].data_ptr(),
+                       g.data_ptr(), k_box, k_cls, k_obj[i], draw.data_ptr(), bp.data_ptr(), st)
+            draws.append(draw)
+            bps.append(bp)
+        if ctx.multi:
+            nl = len(maps)
+            vp = C.c_void_p * nl
+            L.call("cvhip_yolov5_loss_bwd_levels", ctx.darr, nl, vp(*[r.data_ptr() for r in maps]), tg.data_ptr(), ctx.wss[0].data_ptr(),
+                   sums.data_ptr(), g.data_ptr(), k_box, k_cls, (C.c_float * nl)(*k_obj), vp(*[t.data_ptr() for t in draws]),
+                   vp(*[t.data_ptr() for t in bps]), st)
+        for i, (draw, bp) in enumerate(zip(draws, bps)):
+            K = ctx.descs[i].A * ctx.descs[i].NO
             # the detect convolution that receives this map takes its bias gradient from these rows (ops._conv_grads)
             offer_colsum(draw, bp, L.YOLO_BIAS_ROWS, K)
             outs.append(draw.permute(0, 3, 1, 2)[:, :K])

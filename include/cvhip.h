@@ -298,6 +298,18 @@ int cvhip_maxpool2d_fwd(const void* x_bf16, int32_t ld_x, void* y_bf16, int32_t 
 int cvhip_maxpool2d_bwd(const void* dy_bf16, int32_t ld_dy, const uint8_t* argmax, void* dx_bf16,
                         int32_t ld_dx, int32_t N, int32_t C, int32_t H, int32_t W, int32_t k,
                         int32_t stride, int32_t pad, int accumulate, void* stream);
+/* SPPF's pooling chain (yolo_modules.py:186-194: x, m(x), m(m(x)), m(m(m(x))), m = k x k stride-1 "same" max pool) on ONE
+ * (N, H, W, ld >= 4c) buffer whose channel slice j holds stage j; argmax3 = uint8 [3][N][H][W][c], stage j's arg-max bytes.
+ *   fwd : reads slice 0, writes slices 1..3 and argmax3 — values and bytes of three cvhip_maxpool2d_fwd calls, in one launch where the
+ *         map fits the LDS (k = 5, c % 8 == 0, 16-byte aligned pitches), else by those three calls.
+ *   bwd : `buf` holds the gradient of the concatenation; slice 0 becomes the gradient of the chain's input: the value three
+ *         accumulate-form cvhip_maxpool2d_bwd calls (slice j += bwd(slice j + 1), j = 2, 1, 0) leave there, bit for bit, every
+ *         intermediate sum rounded to the 16-bit storage type where that walk stores it. The one-launch form leaves slices 1..3 as
+ *         they came in; the three-call form overwrites slices 1 and 2 with the intermediate sums. Callers may rely on slice 0 only. */
+int cvhip_sppf_chain_fwd(void* buf_bf16, int32_t ld, uint8_t* argmax3, int32_t N, int32_t c, int32_t H, int32_t W, int32_t k,
+                         void* stream);
+int cvhip_sppf_chain_bwd(void* buf_bf16, int32_t ld, const uint8_t* argmax3, int32_t N, int32_t c, int32_t H, int32_t W, int32_t k,
+                         void* stream);
 
 /* out[:, :Ca] = nearest_upsample_x2(a); out[:, Ca:Ca+Cb] = b   — the FPN/PAN "up + cat"
  * (src/models/modules/yolo_modules.py:147,152 UpsamplingModule). b may be NULL (Cb=0). */
@@ -545,6 +557,12 @@ int cvhip_sgd_nesterov_ema_scaled(float* param, const float* grad, float* moment
 int cvhip_i64_add(int64_t* v, int64_t n, int64_t delta, void* stream);
 int cvhip_ema_update(float* ema, const float* src, int64_t n, float decay, const float* dyn_decay,
                      void* stream);
+/* The tail of a train step behind the fused optimizer as ONE launch: cvhip_ema_update(ema, src, n_ema, decay, dyn_decay),
+ * cvhip_i64_add(counters, n_counters, delta) and a zero fill of two byte ranges (the gradient arena and the BatchNorm statistic
+ * accumulators; whole 32-bit words) — the same values as those four calls. Any of the four pieces may be empty (count 0). */
+int cvhip_train_step_tail(float* ema, const float* src, int64_t n_ema, float decay, const float* dyn_decay, int64_t* counters,
+                          int64_t n_counters, int64_t delta, void* zero_a, int64_t bytes_a, void* zero_b, int64_t bytes_b,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * YOLOv5 loss on device, one detection level at a time.
@@ -583,6 +601,21 @@ int cvhip_yolov5_loss_level_bwd(const cvhip_yolo_loss_desc* d, const void* raw_b
 int cvhip_yolov5_loss_level_bwd_bias(const cvhip_yolo_loss_desc* d, const void* raw_bf16, const float* targets, void* ws,
                                      const float* sums4, const float* gout, float k_box, float k_cls, float k_obj,
                                      void* draw_bf16, float* bias_partial, void* stream);
+/* All levels at once (up to CVHIP_YOLO_MAX_LEVELS; `d`, `raws`, `k_obj`, `draws`, `bias_partials` are HOST arrays of `levels` entries,
+ * `sums` is DEVICE fp32 [levels][4]): every stage of level_fwd / level_bwd runs as ONE launch whose grid is the concatenation of the
+ * levels' grids — fwd: clear, candidates, objectness, reductions (4 launches instead of 4 per level); bwd: gradient fill, matched
+ * cells, bias rows (3 instead of 3 per level). Each level's arithmetic, partial-row layout and reduction order are those of the
+ * per-level entries: sums, gradient maps and bias rows are bit-identical to them. `ws` is ONE allocation of
+ * cvhip_yolov5_loss_workspace_bytes_levels bytes (its layout differs from the per-level one: do not mix the two families on one
+ * workspace). bias_partials may be NULL (no bias rows). A level whose pitch is not a multiple of 8 elements takes the per-level
+ * two-pass gradient fill. */
+#define CVHIP_YOLO_MAX_LEVELS 4
+int64_t cvhip_yolov5_loss_workspace_bytes_levels(const cvhip_yolo_loss_desc* d, int32_t levels);
+int cvhip_yolov5_loss_fwd_levels(const cvhip_yolo_loss_desc* d, int32_t levels, const void* const* raws_bf16, const float* targets,
+                                 void* ws, float* sums, void* stream);
+int cvhip_yolov5_loss_bwd_levels(const cvhip_yolo_loss_desc* d, int32_t levels, const void* const* raws_bf16, const float* targets,
+                                 void* ws, const float* sums, const float* gout, float k_box, float k_cls, const float* k_obj,
+                                 void* const* draws_bf16, float* const* bias_partials, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * YOLOv7 OTA label assignment on device (ota_assign.hip) + the loss on that assignment.

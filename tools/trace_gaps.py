@@ -37,3 +37,12 @@ for k, (n, d) in agg.items():
 print("by family (ms):", ", ".join("%s %.2f" % (k, v / 1e6) for k, v in fam.most_common()))
 for k, (n, d) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:45]:
     print("  %5d x %8.1f us = %8.3f ms  %s" % (n, d / n / 1e3, d / 1e6, k[:100]))
+# the small-launch tail: every launch of the step that ran below 10 us, by kernel
+small = collections.defaultdict(lambda: [0, 0])
+for s, e, k in step:
+    if e - s < 10000:
+        small[k][0] += 1
+        small[k][1] += e - s
+print("launches below 10 us: %d of %d, %.3f ms" % (sum(v[0] for v in small.values()), len(step), sum(v[1] for v in small.values()) / 1e6))
+for k, (n, d) in sorted(small.items(), key=lambda kv: -kv[1][1]):
+    print("  %5d x %8.1f us = %8.3f ms  %s" % (n, d / n / 1e3, d / 1e6, k[:100]))
